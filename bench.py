@@ -10,6 +10,13 @@ Rank 0 prints exactly ONE JSON line with the whole-job tokens/sec
 (BASELINE.json metric: "tokens/sec (whole node), auto-searched plan,
 Llama-3-8B on 1/2/4/8 MI355X"). Weak scaling: per-GPU work fixed as N
 grows (global_batch = per-gpu-batch * N).
+
+A plain run sets up, warms up, times the K steps and prints the result
+line.  `--dump-outputs DIR` also writes what the last timed step computed
+(loss, grad norm, a seeded sample of the updated weights and their grads)
+as DIR/<name>.npy; weights and data are seeded, so two builds run with the
+same arguments can be compared output for output.  `--full` adds the
+extras a headline figure does not need (saving the searched plan JSON).
 """
 import argparse
 import json
@@ -121,6 +128,8 @@ def search_bench_plan(cfg, world, args):
     out_path = None
     if os.path.isdir("gpurun_out") and int(os.environ.get("RANK", "0")) == 0:
         out_path = f"gpurun_out/bench_searched_plan_n{world}.json"  # provenance
+    if not getattr(args, "full", False):
+        out_path = None  # a plain run only measures; --full keeps the plan
     best = eng.parallelism_optimization(out_path)
     if best is None:
         return None
@@ -150,6 +159,36 @@ def plan_desc(plan, world: int) -> str:
             f"-ckpt:{sum(plan.checkpoint_flags)}/{n}-chunks{plan.chunks}")
 
 
+DUMP_SAMPLE_PER_BLOCK = 4096  # elements sampled from each optimizer block
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, stats, opt):
+    """Write what the last timed step returned/updated as <name>.npy:
+    loss and grad_norm (float64 scalars), and a fixed seeded sample of
+    every optimizer block's fp32 master weights after the step and of the
+    reduced fp32 grads that step consumed (float32; a few MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.asarray([stats.loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "grad_norm.npy"),
+            np.asarray([opt.last_grad_norm], dtype=np.float64))
+    g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+    params, grads = [], []
+    for b in opt.blocks:
+        master, grad = b.owned_master_and_grad()
+        n = master.numel()
+        idx = torch.randint(0, n, (min(DUMP_SAMPLE_PER_BLOCK, n),),
+                            generator=g).to(master.device)
+        params.append(master.reshape(-1)[idx].float().cpu())
+        grads.append(grad.reshape(-1)[idx].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(params).numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"),
+            torch.cat(grads).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -172,6 +211,12 @@ def main():
     ap.add_argument("--tune-gemms", type=str, default=None,
                     help="TunableOp tuning during warmup; CSV written here "
                          "at exit (then commit as profiles/tunableop_gfx950.csv)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write the last step's "
+                         "outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also do what the headline figure does not need "
+                         "(save the searched plan JSON)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -244,7 +289,11 @@ def main():
             plan = resolve_plan(cfg, world)
     else:
         plan = resolve_plan(cfg, world)
-    model = GalvatronModel(cfg, plan, device=device)
+    # allocate and random-init the weights directly on the GPU (seeded by
+    # cfg.train.seed through torch.manual_seed): drawing 8B bf16 normals on
+    # the host took ~110 s of every run, none of it part of the measurement
+    with torch.device(device):
+        model = GalvatronModel(cfg, plan, device=device)
     opt, sched = get_optimizer_and_param_scheduler(model.stage_model, cfg)
     it = get_train_iterator(cfg, device)
 
@@ -267,8 +316,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    stats = None
     for _ in range(args.steps):
-        one_step()
+        stats = one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -279,6 +329,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0 and stats is not None:
+        dump_outputs(args.dump_outputs, stats, opt)
 
     tokens = args.steps * global_batch * args.seq_len
     value = tokens / elapsed

@@ -82,7 +82,8 @@ __global__ void grad_accum_kernel(float* __restrict__ flat,
 // Multi-tensor sum-of-squares for the global grad norm: one launch over
 // ALL flat grad shards (replaces the per-block eager pow+reduce chain —
 // ~105 launch pairs per step on the 8B bench).  chunks: [n,3] int64
-// (ptr, offset, count); partial[] accumulated with fp32 atomics.
+// (ptr, offset, count); every block writes its partial to out[blockIdx.x]
+// (the caller sums them in a fixed order: same bits on every run).
 __global__ void multi_sumsq_kernel(const long* __restrict__ chunks,
                                    int n_chunks, float* __restrict__ out) {
   float acc = 0.f;
@@ -109,16 +110,21 @@ __global__ void multi_sumsq_kernel(const long* __restrict__ chunks,
   if (threadIdx.x == 0) {
     float t = 0.f;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += warp_acc[w];
-    atomicAdd(out, t);
+    out[blockIdx.x] = t;
   }
 }
 
 }  // namespace
 
+int multi_sumsq_grid(int n_chunks) {
+  int grid = galv_grid(n_chunks * 4);
+  return grid < 1 ? 1 : grid;
+}
+
+// out: multi_sumsq_grid(n_chunks) per-block partial sums
 void multi_sumsq_launch(const long* chunks, int n_chunks, float* out,
                         hipStream_t st) {
-  int grid = galv_grid(n_chunks * 4);
-  if (grid < 1) grid = 1;
+  const int grid = multi_sumsq_grid(n_chunks);
   hipLaunchKernelGGL((multi_sumsq_kernel), dim3(grid), dim3(512), 0, st,
                      chunks, n_chunks, out);
 }

@@ -54,6 +54,7 @@ DECL_MOE(f32_t)
 void flash_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, bool sbhd = false, int window = 0);
 void attn_di_launch(const __bf16*, const __bf16*, float*, int, int, int, int, hipStream_t, bool sbhd = false);
 void flash_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, float* dbias = nullptr, bool sbhd = false, int window = 0);
+int multi_sumsq_grid(int);
 void multi_sumsq_launch(const long*, int, float*, hipStream_t);
 void mfma_probe_launch(const __bf16*, const __bf16*, float*, bool, hipStream_t);
 void decode_attn_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, int, float, const int*, hipStream_t);
@@ -685,10 +686,12 @@ Tensor multi_sumsq(std::vector<Tensor> grads) {
   auto meta_t = at::from_blob(meta.data(), {(long)meta.size()},
                               at::TensorOptions().dtype(at::kLong))
                     .to(dev, /*non_blocking=*/false);
-  auto out = at::zeros({1}, grads[0].options().dtype(at::kFloat));
-  multi_sumsq_launch(meta_t.data_ptr<long>(), (int)(meta.size() / 3),
-                     out.data_ptr<float>(), cur_stream());
-  return out;
+  const int n_chunks = (int)(meta.size() / 3);
+  auto part = at::empty({multi_sumsq_grid(n_chunks)},
+                        grads[0].options().dtype(at::kFloat));
+  multi_sumsq_launch(meta_t.data_ptr<long>(), n_chunks,
+                     part.data_ptr<float>(), cur_stream());
+  return part.sum(0, /*keepdim=*/true);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

@@ -138,27 +138,56 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ dy,
   }
 }
 
-// column-sum of per-block partials: out[c] = sum_g part[g][c]
-// grid.y parallelizes the g dimension (a single serial g-loop per column
-// measured 0.5 ms/call at G=2048); each slice commits one hardware fp32
-// atomic per element into the zero-initialized output.
+// column-sum of per-block partials: out[c] = sum_g part[g][c], in a fixed
+// order so that the result is the same bit for bit on every run.
+// A single serial g-loop per column measured 0.5 ms/call at G=2048, so for
+// large G the sum runs in two passes: colsum_slices_kernel lets grid.y
+// slices of `per` rows each reduce their rows into the slice's first row
+// (in place: every element of a slice is read and written by one thread
+// only), then colsum_kernel adds those first rows (gstep = per).
+__global__ void colsum_slices_kernel(float* __restrict__ part, int G, int H,
+                                     int n_out, int per) {
+  const int g0 = blockIdx.y * per;
+  const int g1 = min(G, g0 + per);
+  if (g0 >= g1) return;
+  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+       idx < (long)n_out * H; idx += (long)gridDim.x * blockDim.x) {
+    const int o = idx / H;
+    const int c = idx - (long)o * H;
+    float acc = 0.f;
+    float* p = part + (long)o * G * H + c;
+    for (int g = g0; g < g1; ++g) acc += p[(long)g * H];
+    p[(long)g0 * H] = acc;
+  }
+}
+
 __global__ void colsum_kernel(const float* __restrict__ part,
                               float* __restrict__ out, int G, int H,
-                              int n_out) {
-  const int g0 = blockIdx.y * ((G + gridDim.y - 1) / gridDim.y);
-  const int g1 = min(G, g0 + (int)((G + gridDim.y - 1) / gridDim.y));
+                              int n_out, int gstep) {
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
        idx < (long)n_out * H; idx += (long)gridDim.x * blockDim.x) {
     const int o = idx / H;
     const int c = idx - (long)o * H;
     float acc = 0.f;
     const float* p = part + (long)o * G * H + c;
-    for (int g = g0; g < g1; ++g) acc += p[(long)g * H];
-    if (gridDim.y == 1)
-      out[idx] = acc;
-    else
-      unsafeAtomicAdd(out + idx, acc);
+    for (int g = 0; g < G; g += gstep) acc += p[(long)g * H];
+    out[idx] = acc;
   }
+}
+
+// part: [n_out][G][H] (clobbered) -> out: [n_out][H]
+static void colsum_launch(float* part, float* out, int G, int H, int n_out,
+                          hipStream_t s) {
+  const dim3 gx(galv_grid(((long)n_out * H + 255) / 256));
+  int gstep = 1;
+  if (G > 64) {
+    const int gy = 32;
+    gstep = (G + gy - 1) / gy;
+    hipLaunchKernelGGL(colsum_slices_kernel, dim3(gx.x, gy), dim3(256), 0, s,
+                       part, G, H, n_out, gstep);
+  }
+  hipLaunchKernelGGL(colsum_kernel, gx, dim3(256), 0, s, part, out, G, H,
+                     n_out, gstep);
 }
 
 template <typename T, int VPT>
@@ -324,10 +353,7 @@ void rmsnorm_bwd_launch_t(const T* dy, const T* x, const T* w,
                                   dw_part, n, H, dsum_in)
   DISPATCH_VPT(H, RUN);
 #undef RUN
-  int gy = grid > 64 ? 32 : 1;
-  hipLaunchKernelGGL(colsum_kernel,
-                     dim3(galv_grid((H + 255) / 256), gy), dim3(256), 0, s,
-                     dw_part, dw, grid, H, 1);
+  colsum_launch(dw_part, dw, grid, H, 1, s);
 }
 
 template <typename T>
@@ -351,10 +377,7 @@ void layernorm_bwd_launch_t(const T* dy, const T* x, const T* w,
                                   dim3(256), 0, s, dy, x, w, mean, invstd, dx, dwdb_part, n, H)
   DISPATCH_VPT(H, RUN);
 #undef RUN
-  int gy = grid > 64 ? 32 : 1;
-  hipLaunchKernelGGL(colsum_kernel,
-                     dim3(galv_grid((2 * H + 255) / 256), gy), dim3(256), 0,
-                     s, dwdb_part, dwdb, grid, H, 2);
+  colsum_launch(dwdb_part, dwdb, grid, H, 2, s);
 }
 
 // explicit instantiations used by bindings.cpp

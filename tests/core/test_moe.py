@@ -91,8 +91,10 @@ def _moe_worker(rank, world, plan_dict, state_path, cfg_extra):
 _BASELINE = {}
 
 
-def get_baseline(tmp_dir="/tmp/galvatron_moe_test"):
+def get_baseline(tmp_dir=None):
     if "v" not in _BASELINE:
+        from tests.utils import scratch_dir
+        tmp_dir = tmp_dir or scratch_dir("galvatron_moe_test")
         from hetu_galvatron_amd.runtime import GalvatronModel
         from hetu_galvatron_amd.runtime.checkpoint.state import (
             canonical_state_from_stage)
@@ -263,8 +265,9 @@ def test_moe_shared_expert_etp2():
     torch.manual_seed(0)
     model = GalvatronModel(cfg)
     state = canonical_state_from_stage(model.stage_model)
-    path = "/tmp/galvatron_moe_test/tiny_moe_shared_state.pt"
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    from tests.utils import scratch_dir
+    path = os.path.join(scratch_dir("galvatron_moe_test"),
+                        "tiny_moe_shared_state.pt")
     torch.save(state, path)
     base_losses = train_steps(model, cfg)
     plan = HybridParallelPlan.uniform(
@@ -309,8 +312,9 @@ def test_moe_etp2_sequential_experts():
     torch.manual_seed(0)
     model = GalvatronModel(cfg)
     state = canonical_state_from_stage(model.stage_model)
-    path = "/tmp/galvatron_moe_test/tiny_moe_seq_state.pt"
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    from tests.utils import scratch_dir
+    path = os.path.join(scratch_dir("galvatron_moe_test"),
+                        "tiny_moe_seq_state.pt")
     torch.save(state, path)
     base_losses = train_steps(model, cfg)
     plan = HybridParallelPlan.uniform(

@@ -56,7 +56,9 @@ def baseline_run(tmp_path_factory_dir=None):
     cfg = make_cfg()
     model = GalvatronModel(cfg)
     state = canonical_state_from_stage(model.stage_model)
-    path = os.path.join(tmp_path_factory_dir or "/tmp", "tiny_llama_state.pt")
+    from tests.utils import scratch_dir
+    path = os.path.join(tmp_path_factory_dir or scratch_dir("galvatron_test"),
+                        "tiny_llama_state.pt")
     torch.save(state, path)
     losses = train_steps(model, cfg)
     return losses, path
@@ -65,9 +67,10 @@ def baseline_run(tmp_path_factory_dir=None):
 _BASELINE = {}
 
 
-def get_baseline(tmp_dir="/tmp/galvatron_test"):
+def get_baseline(tmp_dir=None):
     if "v" not in _BASELINE:
-        os.makedirs(tmp_dir, exist_ok=True)
+        if tmp_dir is not None:
+            os.makedirs(tmp_dir, exist_ok=True)
         _BASELINE["v"] = baseline_run(tmp_dir)
     return _BASELINE["v"]
 
@@ -300,8 +303,9 @@ def get_baseline_with(cfg_extra):
     model = GalvatronModel(cfg)
     state = canonical_state_from_stage(model.stage_model)
     tag = abs(hash(str(sorted(str(cfg_extra))))) % 10**8
-    path = f"/tmp/galvatron_test/tiny_llama_state_{tag}.pt"
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    from tests.utils import scratch_dir
+    path = os.path.join(scratch_dir("galvatron_test"),
+                        f"tiny_llama_state_{tag}.pt")
     torch.save(state, path)
     return train_steps(model, cfg), path
 

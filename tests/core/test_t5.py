@@ -43,8 +43,10 @@ def train_steps(model, cfg, steps=STEPS):
 _BASELINE = {}
 
 
-def get_baseline(tmp_dir="/tmp/galvatron_t5_test"):
+def get_baseline(tmp_dir=None):
     if "v" not in _BASELINE:
+        from tests.utils import scratch_dir
+        tmp_dir = tmp_dir or scratch_dir("galvatron_t5_test")
         from hetu_galvatron_amd.runtime import GalvatronModel
         from hetu_galvatron_amd.runtime.checkpoint.state import (
             canonical_state_from_stage)

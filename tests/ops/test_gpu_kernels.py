@@ -78,6 +78,31 @@ def test_rmsnorm(dtype, shape):
                  math.sqrt(n_rows), what="rmsnorm dw")
 
 
+@pytest.mark.parametrize("rows", [70, 1000])
+def test_norm_weight_grads_reproducible(rows):
+    """dw/db column sums run in a fixed order (no float atomics): repeated
+    calls return the same bits.  More than 64 rows take the two-pass sum;
+    70 rows leave empty slices, 1000 a short last slice."""
+    torch.manual_seed(3)
+    H = 1024
+    x = torch.randn(rows, H, device=dev(), dtype=torch.bfloat16)
+    w = torch.randn(H, device=dev(), dtype=torch.bfloat16) * 0.1 + 1.0
+    b = torch.randn(H, device=dev(), dtype=torch.bfloat16) * 0.1
+    dy = torch.randn_like(x)
+    _, inv = ext().rmsnorm_fwd(x, w, 1e-5)
+    _, mean, invstd = ext().layernorm_fwd(x, w, b, 1e-5)
+    _, dw0 = ext().rmsnorm_bwd(dy, x, w, inv)
+    _, lw0, lb0 = ext().layernorm_bwd(dy, x, w, mean, invstd)
+    _, dw_ref = ref.rmsnorm_bwd(dy.float(), x.float(), w.float(), inv.float())
+    assert_close(dw0, dw_ref, 3e-2 * math.sqrt(rows), what="rmsnorm dw")
+    assert_close(lb0, dy.float().sum(0), 3e-2 * math.sqrt(rows), what="ln db")
+    for _ in range(8):
+        _, dw = ext().rmsnorm_bwd(dy, x, w, inv)
+        _, lw, lb = ext().layernorm_bwd(dy, x, w, mean, invstd)
+        assert torch.equal(dw, dw0)
+        assert torch.equal(lw, lw0) and torch.equal(lb, lb0)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_layernorm(dtype):
     torch.manual_seed(2)
@@ -423,6 +448,17 @@ def test_multi_sumsq():
     got = ext().multi_sumsq(xs)[0]
     want = sum((x.double() ** 2).sum() for x in xs)
     assert abs(float(got) - float(want)) / float(want) < 1e-5, (got, want)
+
+
+def test_multi_sumsq_reproducible():
+    """Per-block partials summed in a fixed order (no float atomics):
+    repeated calls return the same bits."""
+    torch.manual_seed(16)
+    xs = [torch.randn(n, device=dev()).float()
+          for n in (17, 1 << 21, 123457, (1 << 22) + 3)]
+    first = ext().multi_sumsq(xs).clone()
+    for _ in range(8):
+        assert torch.equal(ext().multi_sumsq(xs), first)
 
 
 def test_grad_accum():

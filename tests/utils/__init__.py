@@ -1,1 +1,2 @@
-from .dist_helpers import run_distributed, find_free_port  # noqa: F401
+from .dist_helpers import (  # noqa: F401
+    run_distributed, find_free_port, scratch_dir)

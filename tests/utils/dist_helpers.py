@@ -3,11 +3,27 @@
 (reference: tests/conftest.py:81-195) without requiring torchrun."""
 from __future__ import annotations
 
+import atexit
 import multiprocessing as mp
 import os
+import shutil
 import socket
+import tempfile
 import traceback
 from typing import Any, Callable, Sequence
+
+
+_SCRATCH = {}
+
+
+def scratch_dir(name: str) -> str:
+    """Private temp folder of this test process (removed at exit) for the
+    state files a test hands to its spawned ranks by path."""
+    if name not in _SCRATCH:
+        d = tempfile.mkdtemp(prefix=name + "_")
+        atexit.register(shutil.rmtree, d, ignore_errors=True)
+        _SCRATCH[name] = d
+    return _SCRATCH[name]
 
 
 def find_free_port() -> int:
