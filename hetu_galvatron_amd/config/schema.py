@@ -166,6 +166,18 @@ class DataArgs(BaseModel):
     synthetic_dataset_size: int = 1024
     eod_mask_loss: bool = False  # zero the loss on end-of-document tokens
     eod_token_id: Optional[int] = None  # required when eod_mask_loss
+    # packed documents (reference dataloader flags of the same names): a
+    # document ends AFTER each eod_token_id; attention stays inside a
+    # document (varlen flash attention) / positions restart at 0 per document
+    reset_attention_mask: bool = False
+    reset_position_ids: bool = False
+    # synthetic dataset: write an EOD every ~N tokens (0 = off; needs
+    # eod_token_id) so packed mode can be exercised without a corpus
+    synthetic_mean_doc_length: int = 0
+
+    @property
+    def packed(self) -> bool:
+        return self.reset_attention_mask or self.reset_position_ids
 
 
 class CkptArgs(BaseModel):
@@ -281,4 +293,28 @@ class GalvatronConfig(BaseModel):
             raise ValueError(f"bad mixed_precision {self.parallel.mixed_precision}")
         if self.model.hidden_size % self.model.num_attention_heads != 0:
             raise ValueError("hidden_size must be divisible by num_attention_heads")
+        d = self.data
+        if d.synthetic_mean_doc_length and d.eod_token_id is None:
+            raise ValueError("data.synthetic_mean_doc_length needs "
+                             "data.eod_token_id")
+        if d.packed:
+            # packed documents run the plain local varlen attention path
+            # only; every other combination is refused, never silently
+            # replaced by dense attention
+            what = "data.reset_attention_mask / data.reset_position_ids"
+            if d.eod_token_id is None:
+                raise ValueError(f"{what} need data.eod_token_id")
+            if self.model.model_type == "t5":
+                raise ValueError(f"{what} are not supported for the t5 family")
+            if self.model.sliding_window is not None:
+                raise ValueError(f"{what} do not compose with sliding_window")
+            if self.model.attention_dropout > 0:
+                raise ValueError(
+                    f"{what} do not compose with attention_dropout > 0")
+            if self.parallel.global_cp_deg > 1:
+                raise ValueError(f"{what} do not compose with context "
+                                 "parallelism (cp > 1)")
+            if self.parallel.use_ulysses:
+                raise ValueError(f"{what} do not compose with Ulysses "
+                                 "sequence parallelism")
         return self

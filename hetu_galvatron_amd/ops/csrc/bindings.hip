@@ -54,6 +54,8 @@ DECL_MOE(f32_t)
 void flash_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, bool sbhd = false, int window = 0);
 void attn_di_launch(const __bf16*, const __bf16*, float*, int, int, int, int, hipStream_t, bool sbhd = false);
 void flash_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, float* dbias = nullptr, bool sbhd = false, int window = 0);
+void flash_varlen_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
+void flash_varlen_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
 int multi_sumsq_grid(int);
 void multi_sumsq_launch(const long*, int, float*, hipStream_t);
 void mfma_probe_launch(const __bf16*, const __bf16*, float*, bool, hipStream_t);
@@ -363,6 +365,101 @@ std::vector<Tensor> flash_attn_bwd(
   }
   if (bias.has_value())
     return {dq, dk, dv, dbias};
+  return {dq, dk, dv};
+}
+
+// Packed-document self-attention: cu_seqlens [nseg+1] int32 token offsets
+// into the batch-major flattened [b*s] stream.  The values are NOT read on
+// the host (no sync): the caller validates its host copy (they must tile
+// [0, b*s) without straddling a row, with every length <= max_seqlen), so
+// every output row is written exactly once and at::empty is correct.
+void check_varlen(const Tensor& q, const Tensor& k, const Tensor& v,
+                  const Tensor& cu, int64_t max_seqlen, bool sbhd,
+                  const char* who) {
+  TORCH_CHECK(is_bf16(q) && is_bf16(k) && is_bf16(v), who,
+              ": bf16 only on the native path");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, who,
+              ": q/k/v must be [b,s,h,d] (or [s,b,h,d] with sbhd)");
+  const int64_t s = sbhd ? q.size(0) : q.size(1);
+  const int64_t b = sbhd ? q.size(1) : q.size(0);
+  const int64_t hq = q.size(2), d = q.size(3), hkv = k.size(2);
+  TORCH_CHECK(d == 64 || d == 128, who, ": head dim must be 64|128");
+  TORCH_CHECK(hkv > 0 && hq % hkv == 0, who, ": GQA needs hq % hkv == 0");
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0) &&
+              k.size(1) == q.size(1) && k.size(3) == d, who,
+              ": self-attention only (k/v must match q's b, s and d)");
+  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() &&
+              cu.scalar_type() == at::kInt && cu.dim() == 1 &&
+              cu.numel() >= 2 && cu.device() == q.device(), who,
+              ": cu_seqlens must be a contiguous 1-D int32 tensor on q's "
+              "device with at least 2 entries");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= s, who,
+              ": need 1 <= max_seqlen <= s");
+  TORCH_CHECK(b * s < (1LL << 31), who, ": b*s must fit int32");
+  TORCH_CHECK((cu.numel() - 1) * hq <= 65535, who,
+              ": nseg*hq exceeds the grid limit (65535)");
+}
+
+std::tuple<Tensor, Tensor> flash_attn_varlen_fwd(
+    const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu,
+    int64_t max_seqlen, bool causal, double scale, bool sbhd = false) {
+  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
+  check_varlen(q, k, v, cu, max_seqlen, sbhd, "flash_attn_varlen_fwd");
+  const int b = sbhd ? q.size(1) : q.size(0);
+  const int s = sbhd ? q.size(0) : q.size(1);
+  const int hq = q.size(2), d = q.size(3), hkv = k.size(2);
+  const int nseg = cu.numel() - 1;
+  auto o = at::empty_like(q);
+  auto lse = at::empty({b, hq, s}, q.options().dtype(at::kFloat));
+  flash_varlen_fwd_launch(bfp(q), bfp(k), bfp(v), bfp_mut(o),
+                          lse.data_ptr<float>(), cu.data_ptr<int>(), nseg,
+                          (int)max_seqlen, b, s, hq, hkv, d, (float)scale,
+                          causal, sbhd, cur_stream());
+  return {o, lse};
+}
+
+std::vector<Tensor> flash_attn_varlen_bwd(
+    const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+    const Tensor& o, const Tensor& lse, const Tensor& cu,
+    int64_t max_seqlen, bool causal, double scale, bool sbhd = false) {
+  CHECK_GPU(dout); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o);
+  check_varlen(q, k, v, cu, max_seqlen, sbhd, "flash_attn_varlen_bwd");
+  TORCH_CHECK(is_bf16(dout) && is_bf16(o) && dout.sizes() == q.sizes() &&
+              o.sizes() == q.sizes(),
+              "flash_attn_varlen_bwd: dout/o must be bf16 shaped like q");
+  const int b = sbhd ? q.size(1) : q.size(0);
+  const int s = sbhd ? q.size(0) : q.size(1);
+  const int hq = q.size(2), d = q.size(3), hkv = k.size(2);
+  const int nseg = cu.numel() - 1;
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+              lse.dim() == 3 && lse.size(0) == b && lse.size(1) == hq &&
+              lse.size(2) == s,
+              "flash_attn_varlen_bwd: lse must be fp32 [b, hq, s]");
+  auto lsec = lse.contiguous();
+  auto di = at::empty({b, hq, s}, q.options().dtype(at::kFloat));
+  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, s, hq, d,
+                 cur_stream(), sbhd);
+  auto dq = at::empty_like(q);
+  auto dk_exp = sbhd ? at::empty({s, b, hq, d}, k.options())
+                     : at::empty({b, s, hq, d}, k.options());
+  auto dv_exp = at::empty_like(dk_exp);
+  flash_varlen_bwd_launch(bfp(dout), bfp(q), bfp(k), bfp(v),
+                          lsec.data_ptr<float>(), di.data_ptr<float>(),
+                          bfp_mut(dq), bfp_mut(dk_exp), bfp_mut(dv_exp),
+                          cu.data_ptr<int>(), nseg, (int)max_seqlen, b, s,
+                          hq, hkv, d, (float)scale, causal, sbhd,
+                          cur_stream());
+  Tensor dk = dk_exp, dv = dv_exp;
+  if (hq != hkv) {
+    const int rep = hq / hkv;
+    if (sbhd) {
+      dk = dk_exp.view({s, b, hkv, rep, d}).sum(3);
+      dv = dv_exp.view({s, b, hkv, rep, d}).sum(3);
+    } else {
+      dk = dk_exp.view({b, s, hkv, rep, d}).sum(3);
+      dv = dv_exp.view({b, s, hkv, rep, d}).sum(3);
+    }
+  }
   return {dq, dk, dv};
 }
 
@@ -706,6 +803,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_fwd", &rope_fwd);
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"), py::arg("bias") = py::none(), py::arg("sbhd") = false, py::arg("window") = 0);
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("scale"), py::arg("bias") = py::none(), py::arg("sbhd") = false, py::arg("window") = 0);
+  m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("scale"), py::arg("sbhd") = false);
+  m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("scale"), py::arg("sbhd") = false);
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cur_len"), py::arg("scale"), py::arg("start") = 0);
   m.def("decode_attn_graph", &decode_attn_graph);
   m.def("mfma_probe", &mfma_probe);

@@ -1070,6 +1070,140 @@ void flash_bwd_dkv_kernel(const __bf16* __restrict__ dout,
 }
 
 // ---------------------------------------------------------------------------
+// packed-document (varlen) self-attention: the same block bodies, mapped
+// one workgroup per (segment, head, 256-row block).  cu[nseg+1] holds token
+// offsets into the batch-major flattened [b*s] stream; a segment never
+// straddles a batch row, so it is a contiguous run of rows in both layouts
+// and only the bases change.  sq = skv = len, off = 0.  lse/di keep the
+// dense [b, hq, s] layout.  No complementary pairing: blocks past the end
+// of a short segment leave before touching memory, and mixed lengths are
+// left to the hardware scheduler.
+// ---------------------------------------------------------------------------
+//
+// These kernels are compiled in a translation unit of their own
+// (flash_attn_varlen.hip includes this file with GALV_FLASH_VARLEN_TU set).
+// The block bodies are file-local noinline functions whose LDS base the
+// compiler folds to a constant while the dense kernel is their only caller;
+// a second caller in the same module undoes that folding and costs the
+// dense kernels SGPRs and scratch.  In their own module the dense code
+// objects stay exactly as they were.  Here each body has one call site and
+// is inlined into it (off = 0 and sq == skv fold away; no scratch at D=64).
+#ifdef GALV_FLASH_VARLEN_TU
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wignored-attributes"
+#define VARLEN_INLINE_CALL [[clang::always_inline]]
+
+struct VarlenSeg {
+  int len;        // tokens in the segment (0 = nothing to do)
+  long q_base, kv_base, dkv_base, lse_base;
+  int q_str, kv_str, dkv_str;
+};
+
+template <int D>
+DEV_INLINE VarlenSeg varlen_seg(const int* __restrict__ cu, int b, int s,
+                                int hq, int hkv, bool sbhd) {
+  VarlenSeg g;
+  const int seg = blockIdx.y / hq;
+  const int h = blockIdx.y - seg * hq;
+  const int hk = h / (hq / hkv);
+  const int t0 = cu[seg];
+  const int len = cu[seg + 1] - t0;
+  const int bi = t0 / s;
+  const int p0 = t0 - bi * s;
+  // a malformed table (negative offset, past the last row, straddling a
+  // row) maps to "empty" so no address is ever formed from it
+  const bool ok = t0 >= 0 && len > 0 && bi < b && p0 + len <= s;
+  g.len = ok ? len : 0;
+  g.q_base = sbhd ? (((long)p0 * b + bi) * hq + h) * D
+                  : ((long)t0 * hq + h) * D;
+  g.kv_base = sbhd ? (((long)p0 * b + bi) * hkv + hk) * D
+                   : ((long)t0 * hkv + hk) * D;
+  g.dkv_base = g.q_base;  // dk_exp/dv_exp carry hq heads
+  g.q_str = (sbhd ? b * hq : hq) * D;
+  g.kv_str = (sbhd ? b * hkv : hkv) * D;
+  g.dkv_str = g.q_str;
+  g.lse_base = ((long)bi * hq + h) * s + p0;
+  return g;
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_varlen_fwd_kernel(const __bf16* __restrict__ q,
+                             const __bf16* __restrict__ k,
+                             const __bf16* __restrict__ v,
+                             __bf16* __restrict__ o, float* __restrict__ lse,
+                             const int* __restrict__ cu, int b, int s,
+                             int hq, int hkv, float scale, bool causal,
+                             bool sbhd) {
+  constexpr int KB = 64, QBF = 256;
+  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
+  // workgroup-uniform, before any barrier; also covers len == 0
+  if ((int)blockIdx.x * QBF >= g.len) return;
+  const float sl2e = scale * 1.4426950408889634f;
+  VARLEN_INLINE_CALL flash_fwd_block<D>(
+      blockIdx.x, q, k, v, o, lse, smem, g.q_base, g.kv_base, g.lse_base,
+      g.q_str, g.kv_str, 0, g.len, g.len, sl2e, causal);
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_varlen_bwd_dq_kernel(const __bf16* __restrict__ dout,
+                                const __bf16* __restrict__ q,
+                                const __bf16* __restrict__ k,
+                                const __bf16* __restrict__ v,
+                                const float* __restrict__ lse,
+                                const float* __restrict__ di,
+                                __bf16* __restrict__ dq,
+                                const int* __restrict__ cu, int b, int s,
+                                int hq, int hkv, float scale, bool causal,
+                                bool sbhd) {
+  constexpr int KB = 32, QBF = 256;
+  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
+  if ((int)blockIdx.x * QBF >= g.len) return;
+  VARLEN_INLINE_CALL flash_bwd_dq_block<D>(
+      blockIdx.x, dout, q, k, v, lse, di, dq, smem, g.q_base, g.kv_base,
+      g.lse_base, g.q_str, g.kv_str, 0, g.len, g.len, scale, causal);
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
+                                 const __bf16* __restrict__ q,
+                                 const __bf16* __restrict__ k,
+                                 const __bf16* __restrict__ v,
+                                 const float* __restrict__ lse,
+                                 const float* __restrict__ di,
+                                 __bf16* __restrict__ dk_exp,
+                                 __bf16* __restrict__ dv_exp,
+                                 const int* __restrict__ cu, int b, int s,
+                                 int hq, int hkv, float scale, bool causal,
+                                 bool sbhd) {
+  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
+  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  __shared__ __align__(16) float lsedi[4 * QT];
+  const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
+  if ((int)blockIdx.x * KBW >= g.len) return;
+  // the two phases of flash_bwd_dkv_block, dV then dK
+  VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, false>(
+      blockIdx.x, dout, q, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
+      g.q_base, g.kv_base, g.dkv_base, g.lse_base, g.q_str, g.kv_str,
+      g.dkv_str, 0, g.len, g.len, scale, causal);
+  __syncthreads();
+  VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, true>(
+      blockIdx.x, dout, q, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
+      g.q_base, g.kv_base, g.dkv_base, g.lse_base, g.q_str, g.kv_str,
+      g.dkv_str, 0, g.len, g.len, scale, causal);
+}
+
+#pragma clang diagnostic pop
+#endif  // GALV_FLASH_VARLEN_TU
+
+// ---------------------------------------------------------------------------
 // MFMA layout probe: one-wave 32x32x16 GEMM from global memory laid out by
 // the assumed fragment maps. Validated against torch matmul on-device.
 // ---------------------------------------------------------------------------
@@ -1096,6 +1230,7 @@ __global__ void mfma_probe_kernel(const __bf16* __restrict__ A,  // [32][16]
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
+#ifndef GALV_FLASH_VARLEN_TU
 template <int D>
 static void flash_fwd_launch_d(const __bf16* q, const __bf16* k,
                                const __bf16* v, __bf16* o, float* lse, int b,
@@ -1213,3 +1348,69 @@ void mfma_probe_launch(const __bf16* A, const __bf16* B, float* Dst, bool alt,
     hipLaunchKernelGGL((mfma_probe_kernel<false>), dim3(1), dim3(64), 0, st,
                        A, B, Dst);
 }
+
+#else  // GALV_FLASH_VARLEN_TU
+
+// varlen: grid.x covers the longest segment, grid.y = (segment, head)
+template <int D>
+static void flash_varlen_fwd_launch_d(const __bf16* q, const __bf16* k,
+                                      const __bf16* v, __bf16* o, float* lse,
+                                      const int* cu, int nseg,
+                                      int max_seqlen, int b, int s, int hq,
+                                      int hkv, float scale, bool causal,
+                                      bool sbhd, hipStream_t st) {
+  dim3 grid((max_seqlen + 255) / 256, nseg * hq);
+  hipLaunchKernelGGL((flash_varlen_fwd_kernel<D>), grid, dim3(512), 0, st, q,
+                     k, v, o, lse, cu, b, s, hq, hkv, scale, causal, sbhd);
+}
+
+void flash_varlen_fwd_launch(const __bf16* q, const __bf16* k,
+                             const __bf16* v, __bf16* o, float* lse,
+                             const int* cu, int nseg, int max_seqlen, int b,
+                             int s, int hq, int hkv, int d, float scale,
+                             bool causal, bool sbhd, hipStream_t st) {
+  if (d == 64)
+    flash_varlen_fwd_launch_d<64>(q, k, v, o, lse, cu, nseg, max_seqlen, b,
+                                  s, hq, hkv, scale, causal, sbhd, st);
+  else
+    flash_varlen_fwd_launch_d<128>(q, k, v, o, lse, cu, nseg, max_seqlen, b,
+                                   s, hq, hkv, scale, causal, sbhd, st);
+}
+
+template <int D>
+static void flash_varlen_bwd_launch_d(const __bf16* dout, const __bf16* q,
+                                      const __bf16* k, const __bf16* v,
+                                      const float* lse, const float* di,
+                                      __bf16* dq, __bf16* dk_exp,
+                                      __bf16* dv_exp, const int* cu,
+                                      int nseg, int max_seqlen, int b, int s,
+                                      int hq, int hkv, float scale,
+                                      bool causal, bool sbhd,
+                                      hipStream_t st) {
+  dim3 grid((max_seqlen + 255) / 256, nseg * hq);
+  hipLaunchKernelGGL((flash_varlen_bwd_dq_kernel<D>), grid, dim3(512), 0, st,
+                     dout, q, k, v, lse, di, dq, cu, b, s, hq, hkv, scale,
+                     causal, sbhd);
+  hipLaunchKernelGGL((flash_varlen_bwd_dkv_kernel<D>), grid, dim3(512), 0,
+                     st, dout, q, k, v, lse, di, dk_exp, dv_exp, cu, b, s,
+                     hq, hkv, scale, causal, sbhd);
+}
+
+void flash_varlen_bwd_launch(const __bf16* dout, const __bf16* q,
+                             const __bf16* k, const __bf16* v,
+                             const float* lse, const float* di, __bf16* dq,
+                             __bf16* dk_exp, __bf16* dv_exp, const int* cu,
+                             int nseg, int max_seqlen, int b, int s, int hq,
+                             int hkv, int d, float scale, bool causal,
+                             bool sbhd, hipStream_t st) {
+  if (d == 64)
+    flash_varlen_bwd_launch_d<64>(dout, q, k, v, lse, di, dq, dk_exp, dv_exp,
+                                  cu, nseg, max_seqlen, b, s, hq, hkv, scale,
+                                  causal, sbhd, st);
+  else
+    flash_varlen_bwd_launch_d<128>(dout, q, k, v, lse, di, dq, dk_exp,
+                                   dv_exp, cu, nseg, max_seqlen, b, s, hq,
+                                   hkv, scale, causal, sbhd, st);
+}
+
+#endif  // GALV_FLASH_VARLEN_TU

@@ -9,6 +9,7 @@ Every op here replaces an external CUDA dependency of the reference:
                             (reference: transformer/fused_kernels.py:227-257)
   flash_attention        <- flash_attn_varlen CUDA
                             (reference: transformer/attention_impl.py:18-108)
+  flash_attention_varlen <- the same, with cu_seqlens (packed documents)
 """
 from __future__ import annotations
 
@@ -211,6 +212,77 @@ def flash_attention(q, k, v, causal: bool = True,
     window: mistral-style sliding window (causal only)."""
     o, lse = _FlashAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(),
                                    causal, softmax_scale, window, sbhd)
+    return (o, lse) if return_lse else o
+
+
+def _varlen_native(q) -> bool:
+    return (use_native(q) and q.dtype == torch.bfloat16
+            and q.shape[-1] in (64, 128))
+
+
+class _FlashAttentionVarlen(torch.autograd.Function):
+    """Packed-document self-attention (one cu_seqlens for q and kv).
+    Native path: the flash_varlen_* kernels of ops/csrc/flash_attn.hip;
+    anything else runs the fp32 per-segment reference."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu, max_seqlen, causal, scale, sbhd):
+        if _varlen_native(q):
+            o, lse = get_ext(False).flash_attn_varlen_fwd(
+                q, k, v, cu, max_seqlen, causal, scale, sbhd)
+        else:
+            o, lse = ref.attention_varlen_fwd(q, k, v, cu, max_seqlen,
+                                              causal, scale, sbhd)
+        ctx.save_for_backward(q, k, v, o, lse, cu)
+        ctx.max_seqlen = max_seqlen
+        ctx.causal = causal
+        ctx.scale = scale
+        ctx.sbhd = sbhd
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, dlse):
+        q, k, v, o, lse, cu = ctx.saved_tensors
+        do = do.contiguous()
+        if _varlen_native(q):
+            dq, dk, dv = get_ext(False).flash_attn_varlen_bwd(
+                do, q, k, v, o, lse, cu, ctx.max_seqlen, ctx.causal,
+                ctx.scale, ctx.sbhd)
+        else:
+            dq, dk, dv = ref.attention_varlen_bwd(
+                do, q, k, v, o, lse, cu, ctx.max_seqlen, ctx.causal,
+                ctx.scale, ctx.sbhd)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens, max_seqlen: int,
+                           causal: bool = True,
+                           softmax_scale: Optional[float] = None,
+                           return_lse: bool = False, sbhd: bool = False):
+    """Packed-document flash attention: tokens attend only inside their own
+    segment.  q: [b,s,hq,d]; k,v: [b,s,hkv,d] ([s,b,h,d] with sbhd) ->
+    o like q (+ lse [b,hq,s]).
+
+    cu_seqlens: int32 [nseg+1] token offsets into the batch-major flattened
+    [b*s] stream; the segments tile [0, b*s) and never straddle a batch row
+    (padding is just another segment).  max_seqlen bounds the longest
+    segment, so nothing is read back from the device.  A CPU cu_seqlens is
+    validated here and then copied asynchronously; a device one is trusted
+    (the caller validated its host copy).
+    """
+    b, s = (q.shape[1], q.shape[0]) if sbhd else (q.shape[0], q.shape[1])
+    max_seqlen = int(max_seqlen)
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
+        raise ValueError("cu_seqlens must be a 1-D int32 tensor")
+    if not cu_seqlens.is_cuda:
+        ref.check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
+        if q.is_cuda:
+            cu_seqlens = cu_seqlens.to(q.device, non_blocking=True)
+    scale = softmax_scale if softmax_scale is not None \
+        else 1.0 / math.sqrt(q.shape[-1])
+    o, lse = _FlashAttentionVarlen.apply(
+        q.contiguous(), k.contiguous(), v.contiguous(),
+        cu_seqlens.contiguous(), max_seqlen, causal, scale, sbhd)
     return (o, lse) if return_lse else o
 
 

@@ -264,6 +264,104 @@ def attention_bwd(do, q, k, v, o, lse, causal=True, softmax_scale=None,
     return gq, gk, gv, dsr.sum(0)
 
 
+def check_cu_seqlens(cu_seqlens, b: int, s: int, max_seqlen: int):
+    """Validate packed-document boundaries on the HOST; returns them as a
+    list of ints.
+
+    cu_seqlens: token offsets into the batch-major flattened [b*s] stream.
+    They must start at 0, never decrease, end at b*s, contain every multiple
+    of s (a segment never straddles a batch row) and no segment may be longer
+    than max_seqlen.  A repeated entry is an empty segment and is fine.
+    """
+    cu = [int(x) for x in (cu_seqlens.tolist()
+                           if torch.is_tensor(cu_seqlens) else cu_seqlens)]
+    if len(cu) < 2:
+        raise ValueError("cu_seqlens needs at least 2 entries")
+    if cu[0] != 0:
+        raise ValueError(f"cu_seqlens must start at 0, got {cu[0]}")
+    if cu[-1] != b * s:
+        raise ValueError(
+            f"cu_seqlens must end at b*s = {b * s}, got {cu[-1]} "
+            "(segments tile the whole batch; padding is its own segment)")
+    if not 1 <= max_seqlen <= s:
+        raise ValueError(f"need 1 <= max_seqlen <= s, got {max_seqlen}")
+    for lo, hi in zip(cu[:-1], cu[1:]):
+        if hi < lo:
+            raise ValueError(f"cu_seqlens decreases: {lo} -> {hi}")
+        if hi > lo and (hi - 1) // s != lo // s:
+            raise ValueError(
+                f"segment [{lo}, {hi}) straddles a batch row (s = {s})")
+        if hi - lo > max_seqlen:
+            raise ValueError(
+                f"segment [{lo}, {hi}) is longer than max_seqlen = "
+                f"{max_seqlen}")
+    return cu
+
+
+def _varlen_flat(x, sbhd):
+    """[b,s,h,d] or [s,b,h,d] -> batch-major flattened [b*s, h, d] fp32."""
+    if sbhd:
+        x = x.permute(1, 0, 2, 3)
+    return x.float().reshape(-1, x.shape[-2], x.shape[-1])
+
+
+def _varlen_unflat(x, b, s, sbhd, dtype):
+    x = x.view(b, s, x.shape[-2], x.shape[-1])
+    if sbhd:
+        x = x.permute(1, 0, 2, 3)
+    return x.contiguous().to(dtype)
+
+
+def attention_varlen_fwd(q, k, v, cu_seqlens, max_seqlen, causal=True,
+                         softmax_scale=None, sbhd=False):
+    """Packed-document self-attention: every segment of cu_seqlens attends
+    only to itself.  fp32 loop over the segments on top of attention_fwd.
+
+    q: [b, s, hq, d], k/v: [b, s, hkv, d] ([s, b, h, d] with sbhd).
+    Returns o shaped like q and lse [b, hq, s] — the native layouts.
+    """
+    b, s = (q.shape[1], q.shape[0]) if sbhd else (q.shape[0], q.shape[1])
+    hq, d = q.shape[2], q.shape[3]
+    cu = check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(d)
+    qf, kf, vf = (_varlen_flat(t, sbhd) for t in (q, k, v))
+    o = torch.zeros_like(qf)
+    lse = torch.zeros(b, hq, s, dtype=torch.float32, device=q.device)
+    for t0, t1 in zip(cu[:-1], cu[1:]):
+        if t1 == t0:
+            continue
+        bi, p0 = t0 // s, t0 % s
+        oi, li = attention_fwd(qf[None, t0:t1], kf[None, t0:t1],
+                               vf[None, t0:t1], causal, scale)
+        o[t0:t1] = oi[0]
+        lse[bi, :, p0:p0 + (t1 - t0)] = li[0]
+    return _varlen_unflat(o, b, s, sbhd, q.dtype), lse
+
+
+def attention_varlen_bwd(do, q, k, v, o, lse, cu_seqlens, max_seqlen,
+                         causal=True, softmax_scale=None, sbhd=False):
+    """Backward of attention_varlen_fwd against the PASSED o/lse (like
+    attention_bwd).  Returns dq, dk, dv shaped like q, k, v."""
+    b, s = (q.shape[1], q.shape[0]) if sbhd else (q.shape[0], q.shape[1])
+    d = q.shape[3]
+    cu = check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(d)
+    dof, qf, kf, vf, of = (_varlen_flat(t, sbhd) for t in (do, q, k, v, o))
+    dq, dk, dv = (torch.zeros_like(t) for t in (qf, kf, vf))
+    for t0, t1 in zip(cu[:-1], cu[1:]):
+        if t1 == t0:
+            continue
+        bi, p0 = t0 // s, t0 % s
+        li = lse[bi:bi + 1, :, p0:p0 + (t1 - t0)]
+        gq, gk, gv = attention_bwd(dof[None, t0:t1], qf[None, t0:t1],
+                                   kf[None, t0:t1], vf[None, t0:t1],
+                                   of[None, t0:t1], li, causal, scale)
+        dq[t0:t1], dk[t0:t1], dv[t0:t1] = gq[0], gk[0], gv[0]
+    return (_varlen_unflat(dq, b, s, sbhd, q.dtype),
+            _varlen_unflat(dk, b, s, sbhd, k.dtype),
+            _varlen_unflat(dv, b, s, sbhd, v.dtype))
+
+
 def vocab_ce_stats(logits: torch.Tensor, target: torch.Tensor,
                    vocab_start: int, vocab_end: int):
     """Local-shard stats for vocab-parallel cross entropy.

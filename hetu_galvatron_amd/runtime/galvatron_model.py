@@ -61,6 +61,13 @@ class GalvatronModel(nn.Module):
         world = dist.get_world_size() if dist.is_initialized() else 1
         self.cfg = cfg
         self.plan = plan or resolve_plan(cfg, world)
+        if cfg.data.packed and (any(c > 1 for c in self.plan.cp_sizes_enc)
+                                or self.plan.vcp > 1
+                                or any(self.plan.use_sp)):
+            raise ValueError(
+                "data.reset_attention_mask / data.reset_position_ids do not "
+                "compose with a plan that uses cp > 1 or Ulysses sequence "
+                "parallelism on any layer")
         self.stage_model = build_hybrid_parallel_model(cfg, self.plan, device)
         act_dtype = {"bf16": torch.bfloat16,
                      "fp16": torch.float16}.get(

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from ...config.schema import ModelArgs
 from ...core.comm_groups import LayerCommGroups
+from ..dataloader import packed_cu_seqlens
 from ..redistribute import natural_rows
 from ..tensor_parallel import (
     ColumnParallelLinear, VocabParallelEmbedding, group_rank, group_size,
@@ -40,6 +41,40 @@ def _tag_tp_replicated(*params) -> None:
     for p in params:
         if p is not None:
             p.tp_replicated = True
+
+
+def packed_attention_inputs(ctx: Dict, groups: LayerCommGroups, rotary,
+                            cos, sin, device):
+    """Packed-document inputs of one decoder layer, for ITS dp slice of the
+    microbatch: (cos, sin, cu_seqlens, max_seqlen).
+
+    ctx["doc_boundaries"] (reset_attention_mask) -> cu_seqlens/max_seqlen
+    for flash_attention_varlen; ctx["position_ids"] (reset_position_ids)
+    -> per-row RoPE tables cos/sin[position_ids] shaped [S, b_loc, d/2].
+    Both are memoized in the microbatch ctx and shared by all layers.
+    Without those keys everything passes through unchanged."""
+    if "doc_boundaries" not in ctx and "position_ids" not in ctx:
+        return cos, sin, None, None
+    s = groups.strategy
+    if s.cp > 1 or s.use_ulysses:
+        raise RuntimeError(
+            "packed documents (reset_attention_mask / reset_position_ids) "
+            "do not compose with cp > 1 or Ulysses sequence parallelism")
+    c = groups.coord_of(_my_rank())
+    b_loc = ctx["batch_size"] // s.dp
+    lo, hi = c.dp_idx * b_loc, (c.dp_idx + 1) * b_loc
+    cu = max_seqlen = None
+    if "doc_boundaries" in ctx:
+        cu, max_seqlen = packed_cu_seqlens(ctx, lo, hi, device)
+    if "position_ids" in ctx and cos is not None:
+        cache = ctx.setdefault("_cu_seqlens_cache", {})
+        key = ("rope", lo, hi, rotary.head_dim, rotary.theta, rotary.scaling)
+        hit = cache.get(key)
+        if hit is None:
+            pos = ctx["position_ids"][lo:hi].transpose(0, 1)  # [S, b_loc]
+            hit = cache[key] = (cos[pos].contiguous(), sin[pos].contiguous())
+        cos, sin = hit
+    return cos, sin, cu, max_seqlen
 
 
 class GalvatronEmbedding(nn.Module):
@@ -87,7 +122,18 @@ class GalvatronEmbedding(nn.Module):
             rows = natural_rows(S, s.cp, 1, c.cp_idx, 0, ids.device)
         ids = ids[:, rows]
         h = self.word_embeddings(ids)  # [s_rows(/tp), b_loc, h]
-        if self.position_embeddings is not None:
+        if self.position_embeddings is not None and "position_ids" in ctx:
+            # packed documents: positions restart per document, per row
+            pid = ctx["position_ids"][c.dp_idx * b_loc:(c.dp_idx + 1) * b_loc]
+            pos = self.position_embeddings(
+                pid[:, rows].transpose(0, 1))  # [rows, b_loc, h]
+            if not s.use_ulysses and group_size(self.groups.tp_group) > 1:
+                tp = group_size(self.groups.tp_group)
+                r = group_rank(self.groups.tp_group)
+                sl = pos.shape[0] // tp
+                pos = pos[r * sl:(r + 1) * sl]
+            h = h + pos
+        elif self.position_embeddings is not None:
             pos = self.position_embeddings(rows)  # [rows, h]
             if not s.use_ulysses and group_size(self.groups.tp_group) > 1:
                 # word embedding was reduce-scattered: add the matching slice
@@ -160,9 +206,12 @@ class GalvatronDecoderLayer(nn.Module):
     def forward(self, hidden: torch.Tensor, ctx: Dict) -> torch.Tensor:
         S = ctx["seq_len"]
         cos, sin = self._rope_tables(S, hidden.device)
+        cos, sin, cu_seqlens, max_seqlen = packed_attention_inputs(
+            ctx, self.groups, self.rotary, cos, sin, hidden.device)
         residual = hidden
         x = self.input_norm(hidden)
-        x = self.attention(x, cos, sin)
+        x = self.attention(x, cos, sin, cu_seqlens=cu_seqlens,
+                           max_seqlen=max_seqlen)
         if self.dropout_p > 0 and self.training:
             x = F.dropout(x, self.dropout_p)
         if (self.dropout_p == 0 or not self.training) \

@@ -34,7 +34,7 @@ from ..tensor_parallel.mappings import (
 from ..transformer import RotaryEmbedding
 from ..transformer.attention import SelfAttention
 from ..transformer.norm import build_norm
-from .modules import _my_rank, _tag_tp_replicated
+from .modules import _my_rank, _tag_tp_replicated, packed_attention_inputs
 
 
 class GalvatronMoEMLP(nn.Module):
@@ -176,9 +176,12 @@ class GalvatronMoEDecoderLayer(nn.Module):
     def forward(self, hidden: torch.Tensor, ctx: Dict) -> torch.Tensor:
         S = ctx["seq_len"]
         cos, sin = self._rope_tables(S, hidden.device)
+        cos, sin, cu_seqlens, max_seqlen = packed_attention_inputs(
+            ctx, self.groups, self.rotary, cos, sin, hidden.device)
         residual = hidden
         x = self.input_norm(hidden)
-        x = self.attention(x, cos, sin)
+        x = self.attention(x, cos, sin, cu_seqlens=cu_seqlens,
+                           max_seqlen=max_seqlen)
         if self.dropout_p > 0 and self.training:
             x = F.dropout(x, self.dropout_p)
         hidden = residual + x

@@ -14,6 +14,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from ..dataloader import packed_cu_seqlens  # noqa: F401  (the rows helper)
 from ..models.builder import StageModel
 from . import p2p
 
@@ -51,6 +52,11 @@ def chunk_batch(ctx: Dict, chunks: int, dp: int = 1) -> List[Dict]:
             sub["enc_input_ids"] = ctx["enc_input_ids"][lo:lo + b_mb]
         if "loss_mask" in ctx:
             sub["loss_mask"] = ctx["loss_mask"][lo:lo + b_mb]
+        if "position_ids" in ctx:
+            sub["position_ids"] = ctx["position_ids"][lo:lo + b_mb]
+        if "doc_boundaries" in ctx:
+            sub["doc_boundaries"] = ctx["doc_boundaries"][lo:lo + b_mb]
+            sub["_cu_seqlens_cache"] = {}  # per microbatch, shared by layers
         sub["batch_size"] = b_mb
         out.append(sub)
         lo += b_mb

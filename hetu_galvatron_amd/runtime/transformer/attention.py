@@ -129,9 +129,13 @@ class SelfAttention(nn.Module):
             self.core_attention = None  # plain local flash
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                attn_bias: torch.Tensor = None) -> torch.Tensor:
+                attn_bias: torch.Tensor = None, cu_seqlens=None,
+                max_seqlen: int = None) -> torch.Tensor:
         """x: [s_local, b, h] SBH; cos/sin: tables matching the seq layout at
-        RoPE time (megatron-sp: cp-local full seq; ulysses: the local slice).
+        RoPE time (megatron-sp: cp-local full seq; ulysses: the local slice),
+        [s, d/2] or per-row [s, b, d/2] (packed documents with reset
+        positions).  cu_seqlens/max_seqlen: packed documents — plain local
+        attention only, every other path refuses them.
         attn_bias: additive scores bias (t5 relative bias) — eager fp32
         softmax path; megatron-tp gets [h_local, sq, skv], ulysses the
         full-head table (sliced post-a2a), ring-CP the cp-local rows
@@ -148,6 +152,13 @@ class SelfAttention(nn.Module):
             k = self.k_layernorm(k)
         q, k = apply_rope_qk(q.contiguous(), k.contiguous(), cos, sin,
                              interleaved=self.rope_interleaved)
+        if cu_seqlens is not None and (
+                self.core_attention is not None or attn_bias is not None
+                or self.window is not None or self.attn_dropout > 0):
+            raise RuntimeError(
+                "packed-document attention (cu_seqlens) only runs on the "
+                "plain local path: no cp, Ulysses, bias, sliding window or "
+                "attention dropout")
         if self.attn_dropout > 0 and self.training and attn_bias is None:
             drop = self.attn_dropout
             if isinstance(self.core_attention, DistributedAttention):
@@ -179,7 +190,8 @@ class SelfAttention(nn.Module):
             # (sbhd kernels) — no permute+contiguous copies either way
             o = local_attention(q, k, v.contiguous(), causal=self.causal,
                                 softmax_scale=self.softmax_scale,
-                                window=self.window, sbhd=True)
+                                window=self.window, sbhd=True,
+                                cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
             return self.linear_proj(o.reshape(s, b, -1))
         # [s,b,h,d] -> [b,s,h,d] for the distributed attention paths
         q = q.permute(1, 0, 2, 3).contiguous()

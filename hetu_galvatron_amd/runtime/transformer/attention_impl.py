@@ -20,18 +20,26 @@ import torch
 import torch.distributed as dist
 
 from ...ops import (flash_attention, flash_attention_bwd_only,
-                    flash_attention_fwd_only, flash_bias_attention)
+                    flash_attention_fwd_only, flash_attention_varlen,
+                    flash_bias_attention)
 from ..tensor_parallel.mappings import all_to_all, group_rank, group_size
 
 
 def local_attention(q, k, v, causal: bool = True,
                     softmax_scale: Optional[float] = None,
                     window: Optional[int] = None,
-                    sbhd: bool = False) -> torch.Tensor:
+                    sbhd: bool = False, cu_seqlens=None,
+                    max_seqlen: Optional[int] = None) -> torch.Tensor:
     """Plain local flash attention, autograd-capable. [b, s, h, d]
     (or [s, b, h, d] with sbhd=True — the runtime's native layout, no
     permute copies).  window: mistral sliding window (no-op when
-    window >= kv length)."""
+    window >= kv length).  cu_seqlens/max_seqlen: packed documents —
+    attention stays inside each segment (varlen kernels)."""
+    if cu_seqlens is not None:
+        assert window is None, "packed documents + sliding window"
+        return flash_attention_varlen(q, k, v, cu_seqlens, max_seqlen,
+                                      causal=causal,
+                                      softmax_scale=softmax_scale, sbhd=sbhd)
     return flash_attention(q, k, v, causal=causal, softmax_scale=softmax_scale,
                            window=window, sbhd=sbhd)
 

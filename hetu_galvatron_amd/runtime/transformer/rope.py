@@ -133,6 +133,18 @@ def apply_rope_qk(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor,
     models are rare enough that the fused path stays NEOX-only)."""
     if cos is None:
         return q, k
+    if cos.dim() == 3:
+        # per-row tables [s, b, d/2] (packed documents, positions restart
+        # per document): fold the batch into the row axis — the kernel
+        # indexes its table by row, so [s*b, 1, h, d] with a [s*b, d/2]
+        # table runs the same HIP path
+        s, b = q.shape[0], q.shape[1]
+        cos = cos.reshape(s * b, -1)
+        sin = sin.reshape(s * b, -1)
+        qf, kf = apply_rope_qk(q.reshape(s * b, 1, *q.shape[2:]),
+                               k.reshape(s * b, 1, *k.shape[2:]), cos, sin,
+                               interleaved)
+        return qf.view(q.shape), kf.view(k.shape)
     if interleaved:
         from ...ops.reference_ops import rope_apply_interleaved
         return (rope_apply_interleaved(q, cos, sin),

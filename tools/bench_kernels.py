@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -51,6 +51,65 @@ def bench_flash(iters):
                iters)
     print(f"flash_bwd  b{b} s{s} hq{hq} d{d}: {t*1e3:8.2f} ms  "
           f"{2.5*flops/t/1e12:7.1f} TF/s")
+
+
+def median_of_windows(fn, iters, repeats, warmup=20):
+    """Warm up, then time `repeats` windows of `iters` calls each (every
+    window ends in a device synchronize).  Returns (median, min, max) of the
+    per-call time — the spread is the run-to-run noise of this process."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = sorted(timeit(fn, iters, warmup=0) for _ in range(repeats))
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def bench_varlen(iters, repeats=9, dense_only=False):
+    """Packed-document flash attention vs the dense kernels, bench-shape
+    slice b1 s4096 h32/8 d128 causal bf16, fwd and bwd:
+      dense            flash_attn_fwd/bwd (complementary-pair scheduling)
+      varlen 1x4096    one segment: same work, no pairing
+      varlen 16x256    the same tokens packed as 16 documents
+    Times are medians over `repeats` windows with [min, max].  dense_only
+    skips the varlen rows (to time another build of the extension that
+    predates them with the same code)."""
+    e = ext()
+    b, s, hq, hkv, d = 1, 4096, 32, 8, 128
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn(b, s, hq, d, device="cuda", generator=g).bfloat16()
+    k = torch.randn(b, s, hkv, d, device="cuda", generator=g).bfloat16()
+    v = torch.randn(b, s, hkv, d, device="cuda", generator=g).bfloat16()
+    do = torch.randn(b, s, hq, d, device="cuda", generator=g).bfloat16()
+    scale = 1.0 / math.sqrt(d)
+
+    def row(name, fwd, bwd, pairs):
+        # pairs: causal (q, key) pairs actually attended, per head
+        flops = 4 * b * hq * pairs * d
+        tf, lo, hi = median_of_windows(fwd, iters, repeats)
+        print(f"{name:16s} fwd {tf*1e3:7.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]"
+              f"  {flops/tf/1e12:6.1f} TF/s")
+        tb, lo, hi = median_of_windows(bwd, iters, repeats)
+        print(f"{name:16s} bwd {tb*1e3:7.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]"
+              f"  {2.5*flops/tb/1e12:6.1f} TF/s")
+
+    o, lse = e.flash_attn_fwd(q, k, v, True, scale)
+    row("dense", lambda: e.flash_attn_fwd(q, k, v, True, scale),
+        lambda: e.flash_attn_bwd(do, q, k, v, o, lse, True, scale),
+        s * (s + 1) / 2)
+    if dense_only:
+        return
+    for nseg in (1, 16):
+        L = s // nseg
+        cu = torch.arange(0, s + 1, L, dtype=torch.int32, device="cuda")
+        ov, lsev = e.flash_attn_varlen_fwd(q, k, v, cu, L, True, scale)
+        if nseg == 1:
+            assert torch.equal(ov, o) and torch.equal(lsev, lse), \
+                "varlen with one segment must reproduce the dense kernel"
+        row(f"varlen {nseg}x{L}",
+            lambda: e.flash_attn_varlen_fwd(q, k, v, cu, L, True, scale),
+            lambda: e.flash_attn_varlen_bwd(do, q, k, v, ov, lsev, cu, L,
+                                            True, scale),
+            nseg * L * (L + 1) / 2)
 
 
 def bench_norms(iters):
@@ -134,11 +193,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=9,
+                    help="timed windows per row (varlen entry)")
+    ap.add_argument("--dense-only", action="store_true",
+                    help="varlen entry: time only the dense kernels")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     fns = {"flash": bench_flash, "norms": bench_norms,
            "elementwise": bench_elementwise, "adam": bench_adam,
-           "bias": bench_bias}
+           "bias": bench_bias,
+           "varlen": lambda it: bench_varlen(it, args.repeats,
+                                             args.dense_only)}
     if args.what == "all":
         for f in fns.values():
             f(args.iters)
