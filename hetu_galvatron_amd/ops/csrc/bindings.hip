@@ -56,6 +56,10 @@ void attn_di_launch(const __bf16*, const __bf16*, float*, int, int, int, int, hi
 void flash_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, float* dbias = nullptr, bool sbhd = false, int window = 0);
 void flash_varlen_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
 void flash_varlen_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
+void flash_packed_fwd_launch(const __bf16*, __bf16*, float*, int, int, int, int, int, float, bool, hipStream_t);
+void flash_packed_bwd_launch(const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, float, bool, hipStream_t);
+void rope_qkv_launch(__bf16*, const float*, const float*, long, int, int, int, hipStream_t);
+void qkv_grad_finish_launch(__bf16*, const __bf16*, const __bf16*, const float*, const float*, long, int, int, int, hipStream_t);
 int multi_sumsq_grid(int);
 void multi_sumsq_launch(const long*, int, float*, hipStream_t);
 void mfma_probe_launch(const __bf16*, const __bf16*, float*, bool, hipStream_t);
@@ -463,6 +467,123 @@ std::vector<Tensor> flash_attn_varlen_bwd(
   return {dq, dk, dv};
 }
 
+// ---- packed-QKV attention ---------------------------------------------------
+// qkv is the linear_qkv output viewed [s, b, G, qpg+2, d] (G local kv
+// groups; q heads in slots 0..qpg-1 of a group, k in slot qpg, v in slot
+// qpg+1).  The kernels read q, k and v from it in place.
+void check_qkv(const Tensor& qkv, const char* who) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && is_bf16(qkv) &&
+              qkv.dim() == 5 && qkv.size(3) >= 3, who,
+              ": qkv must be a contiguous bf16 GPU tensor [s,b,G,qpg+2,d]");
+  const int64_t d = qkv.size(4);
+  TORCH_CHECK(d == 64 || d == 128, who, ": head dim must be 64|128");
+  TORCH_CHECK(qkv.size(0) >= 1 && qkv.size(1) >= 1 && qkv.size(2) >= 1, who,
+              ": empty qkv");
+  TORCH_CHECK(qkv.size(1) * qkv.size(2) * qkv.size(3) * d < (1LL << 31),
+              who, ": row stride must fit int32");
+  TORCH_CHECK(qkv.size(1) * qkv.size(2) * (qkv.size(3) - 2) <= 65535, who,
+              ": b*hq exceeds the grid limit (65535)");
+}
+
+void check_rope_tables(const Tensor& qkv, const Tensor& cos_t,
+                       const Tensor& sin_t, const char* who) {
+  TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() &&
+              cos_t.scalar_type() == at::kFloat &&
+              sin_t.scalar_type() == at::kFloat && cos_t.is_contiguous() &&
+              sin_t.is_contiguous() && cos_t.dim() == 2 &&
+              cos_t.sizes() == sin_t.sizes() &&
+              cos_t.size(0) == qkv.size(0) &&
+              cos_t.size(1) * 2 == qkv.size(4), who,
+              ": cos/sin must be contiguous fp32 [s, d/2] on the GPU");
+}
+
+// In-place NEOX RoPE on the q and k slots; v is not touched.
+void rope_qkv_(Tensor qkv, const Tensor& cos_t, const Tensor& sin_t) {
+  check_qkv(qkv, "rope_qkv_");
+  check_rope_tables(qkv, cos_t, sin_t, "rope_qkv_");
+  const long groups = qkv.size(0) * qkv.size(1) * qkv.size(2);
+  rope_qkv_launch(bfp_mut(qkv), cos_t.data_ptr<float>(),
+                  sin_t.data_ptr<float>(), groups,
+                  (int)(qkv.size(1) * qkv.size(2)), (int)qkv.size(3) - 2,
+                  (int)qkv.size(4), cur_stream());
+}
+
+// -> o [s, b, hq, d], lse [b, hq, s]
+std::tuple<Tensor, Tensor> flash_attn_qkv_fwd(const Tensor& qkv, bool causal,
+                                              double scale) {
+  check_qkv(qkv, "flash_attn_qkv_fwd");
+  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
+  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
+  auto o = at::empty({s, b, G * qpg, d}, qkv.options());
+  auto lse = at::empty({b, G * qpg, s}, qkv.options().dtype(at::kFloat));
+  flash_packed_fwd_launch(bfp(qkv), bfp_mut(o), lse.data_ptr<float>(), b, s,
+                          G, qpg, d, (float)scale, causal, cur_stream());
+  return {o, lse};
+}
+
+// -> dqkv (q slots = dq before the inverse rotation, k and v slots NOT yet
+// written), dk_exp, dv_exp [s, b, hq, d].  qkv_grad_finish_ completes dqkv.
+std::vector<Tensor> flash_attn_qkv_bwd(const Tensor& dout, const Tensor& qkv,
+                                       const Tensor& o, const Tensor& lse,
+                                       bool causal, double scale) {
+  check_qkv(qkv, "flash_attn_qkv_bwd");
+  CHECK_GPU(dout); CHECK_GPU(o); CHECK_GPU(lse);
+  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
+  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
+  const int hq = G * qpg;
+  TORCH_CHECK(is_bf16(dout) && is_bf16(o) && o.dim() == 4 &&
+              o.size(0) == s && o.size(1) == b && o.size(2) == hq &&
+              o.size(3) == d && dout.sizes() == o.sizes(),
+              "flash_attn_qkv_bwd: dout/o must be bf16 [s, b, hq, d]");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 &&
+              lse.size(0) == b && lse.size(1) == hq && lse.size(2) == s,
+              "flash_attn_qkv_bwd: lse must be fp32 [b, hq, s]");
+  auto di = at::empty({b, hq, s}, qkv.options().dtype(at::kFloat));
+  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, s, hq, d,
+                 cur_stream(), /*sbhd=*/true);
+  // at::empty: the dq kernel writes every q-slot element and
+  // qkv_grad_finish_ writes every k- and v-slot element, each exactly once
+  auto dqkv = at::empty_like(qkv);
+  auto dk_exp = at::empty({s, b, hq, d}, qkv.options());
+  auto dv_exp = at::empty({s, b, hq, d}, qkv.options());
+  flash_packed_bwd_launch(bfp(dout), bfp(qkv), lse.data_ptr<float>(),
+                          di.data_ptr<float>(), bfp_mut(dqkv),
+                          bfp_mut(dk_exp), bfp_mut(dv_exp), b, s, G, qpg, d,
+                          (float)scale, causal, cur_stream());
+  return {dqkv, dk_exp, dv_exp};
+}
+
+// One pass that turns dqkv into the gradient of the linear_qkv output:
+// inverse rotation of the q slots, GQA group sum of dk_exp / dv_exp into the
+// k / v slots (k rotated back too).  No cos/sin: no rotary embedding.
+void qkv_grad_finish_(Tensor dqkv, const Tensor& dk_exp, const Tensor& dv_exp,
+                      const c10::optional<Tensor>& cos_t,
+                      const c10::optional<Tensor>& sin_t) {
+  check_qkv(dqkv, "qkv_grad_finish_");
+  CHECK_GPU(dk_exp); CHECK_GPU(dv_exp);
+  const int64_t hq = dqkv.size(2) * (dqkv.size(3) - 2);
+  TORCH_CHECK(is_bf16(dk_exp) && dk_exp.dim() == 4 &&
+              dk_exp.size(0) == dqkv.size(0) &&
+              dk_exp.size(1) == dqkv.size(1) && dk_exp.size(2) == hq &&
+              dk_exp.size(3) == dqkv.size(4) && is_bf16(dv_exp) &&
+              dv_exp.sizes() == dk_exp.sizes(),
+              "qkv_grad_finish_: dk_exp/dv_exp must be bf16 [s, b, hq, d]");
+  TORCH_CHECK(cos_t.has_value() == sin_t.has_value(),
+              "qkv_grad_finish_: cos and sin go together");
+  const float* cp = nullptr;
+  const float* sp = nullptr;
+  if (cos_t.has_value()) {
+    check_rope_tables(dqkv, *cos_t, *sin_t, "qkv_grad_finish_");
+    cp = cos_t->data_ptr<float>();
+    sp = sin_t->data_ptr<float>();
+  }
+  const long groups = dqkv.size(0) * dqkv.size(1) * dqkv.size(2);
+  qkv_grad_finish_launch(bfp_mut(dqkv), bfp(dk_exp), bfp(dv_exp), cp, sp,
+                         groups, (int)(dqkv.size(1) * dqkv.size(2)),
+                         (int)dqkv.size(3) - 2, (int)dqkv.size(4),
+                         cur_stream());
+}
+
 // Single-token decode attention against a KV cache (serving path).
 // q: [b,hq,d]; k_cache/v_cache: [b,max_s,hkv,d]; attends to [0, cur_len).
 Tensor decode_attn(const Tensor& q, const Tensor& k_cache,
@@ -805,6 +926,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("scale"), py::arg("bias") = py::none(), py::arg("sbhd") = false, py::arg("window") = 0);
   m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("scale"), py::arg("sbhd") = false);
   m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("scale"), py::arg("sbhd") = false);
+  m.def("rope_qkv_", &rope_qkv_, py::arg("qkv"), py::arg("cos"), py::arg("sin"));
+  m.def("flash_attn_qkv_fwd", &flash_attn_qkv_fwd, py::arg("qkv"), py::arg("causal"), py::arg("scale"));
+  m.def("flash_attn_qkv_bwd", &flash_attn_qkv_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("scale"));
+  m.def("qkv_grad_finish_", &qkv_grad_finish_, py::arg("dqkv"), py::arg("dk_exp"), py::arg("dv_exp"), py::arg("cos") = py::none(), py::arg("sin") = py::none());
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cur_len"), py::arg("scale"), py::arg("start") = 0);
   m.def("decode_attn_graph", &decode_attn_graph);
   m.def("mfma_probe", &mfma_probe);

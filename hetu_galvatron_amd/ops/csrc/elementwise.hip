@@ -97,7 +97,157 @@ __global__ void rope_kernel(const T* __restrict__ x, T* __restrict__ y,
   }
 }
 
+// rope_kernel's rotation of one 8-element packet pair, with the fused
+// multiply-adds spelled out.  rope_kernel leaves the contraction of
+// a*c - b*s and b*c + a*s to the compiler, which fuses the cos product
+// into the fma and rounds the sin product on its own; the packed kernels
+// vectorise differently and would otherwise get a different mix of fused
+// and unfused products.  Spelled out, their bits equal rope_kernel's
+// (asserted on the GPU in tests/ops/test_gpu_fused_qkv.py).
+template <bool CONJ>
+DEV_INLINE void rope_rotate8(const float* a, const float* b, const float* c,
+                             const float* s, float* o1, float* o2) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float sv = CONJ ? -s[i] : s[i];
+    o1[i] = __builtin_fmaf(a[i], c[i], -(b[i] * sv));
+    o2[i] = __builtin_fmaf(b[i], c[i], a[i] * sv);
+  }
+}
+
+// In-place RoPE on the packed linear_qkv output x: [s, b, G, qpg+2, d]
+// (G kv groups; slots 0..qpg-1 of a group are its q heads, slot qpg is k,
+// slot qpg+1 is v).  Rotates the q and k slots and never touches v.
+// groups = s*b*G, bG = b*G.  Same arithmetic as rope_kernel (fp32, NEOX
+// halves, 16-byte packets, [s, d/2] tables), so the rotated q and k bits
+// equal those of the split-then-rotate path.  Each packet pair is read and
+// written by the same thread: safe in place.
+__global__ void rope_qkv_kernel(__bf16* __restrict__ x,
+                                const float* __restrict__ cos_t,
+                                const float* __restrict__ sin_t,
+                                long groups, int bG, int qpg, int d) {
+  const int d2 = d / 2;
+  const long packs_per_row = d2 / 8;
+  const long per_group = (qpg + 1) * packs_per_row;
+  const long total = groups * per_group;
+  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
+       idx += (long)gridDim.x * blockDim.x) {
+    const long grp = idx / per_group;
+    const long r = idx - grp * per_group;
+    const long slot = r / packs_per_row;
+    const long j = (r - slot * packs_per_row) * 8;
+    const long s_idx = grp / bG;
+    __bf16* x1 = x + (grp * (qpg + 2) + slot) * (long)d + j;
+    __bf16* x2 = x1 + d2;
+    float a[8], b[8], c[8], s[8], o1[8], o2[8];
+    VecIO<__bf16>::load(a, x1);
+    VecIO<__bf16>::load(b, x2);
+    VecIO<float>::load(c, cos_t + s_idx * d2 + j);
+    VecIO<float>::load(s, sin_t + s_idx * d2 + j);
+    rope_rotate8<false>(a, b, c, s, o1, o2);
+    VecIO<__bf16>::store(x1, o1);
+    VecIO<__bf16>::store(x2, o2);
+  }
+}
+
+// Finishes the gradient of the packed linear_qkv output in one pass over
+// dqkv [s, b, G, qpg+2, d], whose q slots already hold dq (written by the
+// packed flash backward) and whose k and v slots are still unwritten:
+//   q slots  inverse rotation in place
+//   k slot   fp32 sum of the group's qpg heads of dk_exp [s, b, G*qpg, d],
+//            rounded to bf16 (the GQA reduction's rounding), then the
+//            inverse rotation
+//   v slot   the same sum of dv_exp
+// Every element of the k and v slots is written exactly once.  ROPE = false
+// (no rotary embedding) compiles the rotation out and skips the q slots.
+template <bool ROPE>
+__global__ void qkv_grad_finish_kernel(__bf16* __restrict__ dqkv,
+                                       const __bf16* __restrict__ dk_exp,
+                                       const __bf16* __restrict__ dv_exp,
+                                       const float* __restrict__ cos_t,
+                                       const float* __restrict__ sin_t,
+                                       long groups, int bG, int qpg, int d) {
+  const int d2 = d / 2;
+  const long packs_per_row = d2 / 8;
+  const int first = ROPE ? 0 : qpg;
+  const long per_group = (qpg + 2 - first) * packs_per_row;
+  const long total = groups * per_group;
+  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
+       idx += (long)gridDim.x * blockDim.x) {
+    const long grp = idx / per_group;
+    const long r = idx - grp * per_group;
+    const long sl = r / packs_per_row;
+    const long slot = first + sl;
+    const long j = (r - sl * packs_per_row) * 8;
+    __bf16* x1 = dqkv + (grp * (qpg + 2) + slot) * (long)d + j;
+    __bf16* x2 = x1 + d2;
+    float a[8], b[8];
+    if (slot < qpg) {
+      VecIO<__bf16>::load(a, x1);
+      VecIO<__bf16>::load(b, x2);
+    } else {
+      const __bf16* e1 =
+          (slot == qpg ? dk_exp : dv_exp) + grp * qpg * (long)d + j;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a[i] = b[i] = 0.f;
+      for (int h = 0; h < qpg; ++h) {
+        float ta[8], tb[8];
+        VecIO<__bf16>::load(ta, e1 + h * (long)d);
+        VecIO<__bf16>::load(tb, e1 + h * (long)d + d2);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          a[i] += ta[i];
+          b[i] += tb[i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        a[i] = (float)(__bf16)a[i];
+        b[i] = (float)(__bf16)b[i];
+      }
+    }
+    if (ROPE && slot <= qpg) {
+      const long s_idx = grp / bG;
+      float c[8], s[8], o1[8], o2[8];
+      VecIO<float>::load(c, cos_t + s_idx * d2 + j);
+      VecIO<float>::load(s, sin_t + s_idx * d2 + j);
+      rope_rotate8<true>(a, b, c, s, o1, o2);
+      VecIO<__bf16>::store(x1, o1);
+      VecIO<__bf16>::store(x2, o2);
+    } else {
+      VecIO<__bf16>::store(x1, a);
+      VecIO<__bf16>::store(x2, b);
+    }
+  }
+}
+
 }  // namespace
+
+void rope_qkv_launch(__bf16* x, const float* cos_t, const float* sin_t,
+                     long groups, int bG, int qpg, int d, hipStream_t st) {
+  long total = groups * (qpg + 1) * (d / 2 / 8);
+  int grid = galv_grid((total + 255) / 256);
+  hipLaunchKernelGGL(rope_qkv_kernel, dim3(grid), dim3(256), 0, st, x, cos_t,
+                     sin_t, groups, bG, qpg, d);
+}
+
+// cos_t == nullptr: no rotary embedding
+void qkv_grad_finish_launch(__bf16* dqkv, const __bf16* dk_exp,
+                            const __bf16* dv_exp, const float* cos_t,
+                            const float* sin_t, long groups, int bG, int qpg,
+                            int d, hipStream_t st) {
+  const bool rope = cos_t != nullptr;
+  long total = groups * (rope ? qpg + 2 : 2) * (d / 2 / 8);
+  int grid = galv_grid((total + 255) / 256);
+  if (rope)
+    hipLaunchKernelGGL((qkv_grad_finish_kernel<true>), dim3(grid), dim3(256),
+                       0, st, dqkv, dk_exp, dv_exp, cos_t, sin_t, groups, bG,
+                       qpg, d);
+  else
+    hipLaunchKernelGGL((qkv_grad_finish_kernel<false>), dim3(grid),
+                       dim3(256), 0, st, dqkv, dk_exp, dv_exp, cos_t, sin_t,
+                       groups, bG, qpg, d);
+}
 
 template <typename T>
 void swiglu_fwd_launch_t(const T* x, T* y, long rows, int F, hipStream_t st) {

@@ -58,10 +58,27 @@ DEV_INLINE void load_bias16(const __bf16* brow, int base, int limit,
   }
 }
 
+// Where the o / dout rows of a head live.  The dense and varlen kernels keep
+// them at q's base and row stride (OutLikeQ: an empty tag, nothing is
+// passed and the address arithmetic is unchanged); the packed-QKV kernels
+// read q from the linear_qkv buffer while o / dout stay [s, b, hq, D], so
+// they pass a base and a stride of their own (OutOwn).
+struct OutLikeQ {
+  DEV_INLINE long base(long q_base) const { return q_base; }
+  DEV_INLINE int stride(int q_stride) const { return q_stride; }
+};
+struct OutOwn {
+  long o_base;
+  int o_stride;
+  DEV_INLINE long base(long) const { return o_base; }
+  DEV_INLINE int stride(int) const { return o_stride; }
+};
+
 // ---------------------------------------------------------------------------
 // forward (v2)
 // ---------------------------------------------------------------------------
-template <int D, bool BIASED = false, bool WINDOWED = false>
+template <int D, bool BIASED = false, bool WINDOWED = false,
+          class OA = OutLikeQ>
 __device__ __attribute__((noinline))
 void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
                      const __bf16* __restrict__ k,
@@ -71,7 +88,7 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
                      long lse_base, int q_stride, int kv_stride, int off,
                      int sq, int skv, float sl2e, bool causal,
                      const __bf16* __restrict__ bias = nullptr,
-                     long bias_base = 0, int window = 0) {
+                     long bias_base = 0, int window = 0, OA oa = OA()) {
   constexpr int KB = 64;            // kv tile
   constexpr int QBF = 256;          // q rows per workgroup (8 waves x 32)
   constexpr int KROW = D + 8;       // padded K row (bf16 elems)
@@ -315,7 +332,7 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
   const int qg = q0w + col;
   if (qg < sq) {
     const float invl = l_run > 0.f ? 1.f / l_run : 0.f;
-    __bf16* orow = o + q_base + (long)qg * q_stride;
+    __bf16* orow = o + oa.base(q_base) + (long)qg * oa.stride(q_stride);
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -422,7 +439,8 @@ __global__ void attn_di_kernel(const __bf16* __restrict__ dout,
 // the v1 form spilled 34 dwords/lane to scratch).
 // dQ^T[d][q] += K^T dS accumulated in D-layout, epilogue like the forward.
 // ---------------------------------------------------------------------------
-template <int D, bool BIASED = false, bool WINDOWED = false>
+template <int D, bool BIASED = false, bool WINDOWED = false,
+          class OA = OutLikeQ>
 __device__ __attribute__((noinline))
 void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
                         const __bf16* __restrict__ q,
@@ -435,7 +453,7 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
                         int q_stride, int kv_stride, int off, int sq,
                         int skv, float scale, bool causal,
                         const __bf16* __restrict__ bias = nullptr,
-                        long bias_base = 0, int window = 0) {
+                        long bias_base = 0, int window = 0, OA oa = OA()) {
   constexpr int KB = 32;         // kv tile
   constexpr int QBF = 256;       // q rows per workgroup (8 waves x 32)
   constexpr int KROW = D + 8;
@@ -459,7 +477,8 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
   {
     const int qg = min(q0w + col, sq - 1);
     const __bf16* qp = q + q_base + (long)qg * q_stride + 8 * hi;
-    const __bf16* dop = dout + q_base + (long)qg * q_stride + 8 * hi;
+    const __bf16* dop = dout + oa.base(q_base) +
+                        (long)qg * oa.stride(q_stride) + 8 * hi;
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks) {
       qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
@@ -715,7 +734,8 @@ void flash_bwd_dq_kernel(const __bf16* __restrict__ dout,
 //   phase dK:  S again; dP = mfma(dO_frag[from do_lds rows], V^T[vfr regs])
 //              dK^T[d][key] = mfma(Q^T_frag[from t_lds], dS_frag[permlane])
 // ---------------------------------------------------------------------------
-template <int D, bool DKPH, bool BIASED = false, bool WINDOWED = false>
+template <int D, bool DKPH, bool BIASED = false, bool WINDOWED = false,
+          class OA = OutLikeQ>
 __device__ __attribute__((noinline))
 void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
                          const __bf16* __restrict__ q,
@@ -731,7 +751,7 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
                          int skv, float scale, bool causal,
                          const __bf16* __restrict__ bias = nullptr,
                          float* __restrict__ dbias = nullptr,
-                         long bias_base = 0, int window = 0) {
+                         long bias_base = 0, int window = 0, OA oa = OA()) {
   constexpr int QT = 64;           // q tile (2 mfma halves per stage)
   constexpr int KBW = 256;         // keys per workgroup (8 waves x 32)
   constexpr int QROW = D + 8;
@@ -789,6 +809,10 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
   ushort8 ttst[QPT];
   float lse_st, di_st;
   const __bf16* tsrc = DKPH ? q : dout;  // transposed-image source
+  const long do_base = oa.base(q_base);
+  const int do_stride = oa.stride(q_stride);
+  const long t_base = DKPH ? q_base : do_base;
+  const int t_stride = DKPH ? q_stride : do_stride;
 
   auto stage_load = [&](int qt0) {
     const bool full = (qt0 + QT <= sq);
@@ -803,7 +827,7 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
           q + q_base + (long)qg * q_stride + c8);
       if (DKPH)
         dost[p] = *reinterpret_cast<const bf16x8*>(
-            dout + q_base + (long)qg * q_stride + c8);
+            dout + do_base + (long)qg * do_stride + c8);
       if (!full && qt0 + row >= sq) {
         qst[p] = (bf16x8)(__bf16(0.f));
         if (DKPH) dost[p] = (bf16x8)(__bf16(0.f));
@@ -816,16 +840,16 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
       const int c = idx & (D - 1);
       const int qc = (idx / D) * 8;
       const unsigned short* tb = reinterpret_cast<const unsigned short*>(
-          tsrc + q_base) + c;
+          tsrc + t_base) + c;
       ushort8 t8;
       if (full) {
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          t8[j] = tb[(long)(qt0 + qc + j) * q_stride];
+          t8[j] = tb[(long)(qt0 + qc + j) * t_stride];
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          unsigned short a = tb[(long)min(qt0 + qc + j, sq - 1) * q_stride];
+          unsigned short a = tb[(long)min(qt0 + qc + j, sq - 1) * t_stride];
           t8[j] = qt0 + qc + j < sq ? a : (unsigned short)0;
         }
       }
@@ -992,7 +1016,8 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
   }
 }
 
-template <int D, bool BIASED = false, bool WINDOWED = false>
+template <int D, bool BIASED = false, bool WINDOWED = false,
+          class OA = OutLikeQ>
 __device__ void flash_bwd_dkv_block(
     int kvblk, const __bf16* __restrict__ dout, const __bf16* __restrict__ q,
     const __bf16* __restrict__ k, const __bf16* __restrict__ v,
@@ -1002,16 +1027,16 @@ __device__ void flash_bwd_dkv_block(
     long dkv_base, long lse_base, int q_stride, int kv_stride,
     int dkv_stride, int off, int sq, int skv, float scale, bool causal,
     const __bf16* bias = nullptr, float* dbias = nullptr,
-    long bias_base = 0, int window = 0) {
-  flash_bwd_dkv_phase<D, false, BIASED, WINDOWED>(
+    long bias_base = 0, int window = 0, OA oa = OA()) {
+  flash_bwd_dkv_phase<D, false, BIASED, WINDOWED, OA>(
       kvblk, dout, q, k, v, lse, di, dk_exp, dv_exp, smem_base, lsedi_base,
       q_base, kv_base, dkv_base, lse_base, q_stride, kv_stride, dkv_stride,
-      off, sq, skv, scale, causal, bias, dbias, bias_base, window);
+      off, sq, skv, scale, causal, bias, dbias, bias_base, window, oa);
   __syncthreads();
-  flash_bwd_dkv_phase<D, true, BIASED, WINDOWED>(
+  flash_bwd_dkv_phase<D, true, BIASED, WINDOWED, OA>(
       kvblk, dout, q, k, v, lse, di, dk_exp, dv_exp, smem_base, lsedi_base,
       q_base, kv_base, dkv_base, lse_base, q_stride, kv_stride, dkv_stride,
-      off, sq, skv, scale, causal, bias, dbias, bias_base, window);
+      off, sq, skv, scale, causal, bias, dbias, bias_base, window, oa);
 }
 
 template <int D, bool BIASED = false, bool WINDOWED = false>
@@ -1204,6 +1229,153 @@ void flash_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
 #endif  // GALV_FLASH_VARLEN_TU
 
 // ---------------------------------------------------------------------------
+// packed-QKV self-attention: the same block bodies reading q, k and v
+// straight from the linear_qkv output [s, b, G, qpg+2, D] (G local kv
+// groups; slots 0..qpg-1 of a group are its q heads, slot qpg is k, slot
+// qpg+1 is v), so nothing has to separate them in memory first.  sbhd only,
+// sq = skv = s, off = 0, no bias, no window.
+//   row stride (q, k, v, dq)   b*G*(qpg+2)*D
+//   q / dq head base           ((bi*G + h/qpg)*(qpg+2) + h%qpg)*D
+//   k, v                       slots qpg, qpg+1 of group h/qpg: the k and v
+//                              pointers are pre-offset by qpg*D, (qpg+1)*D
+//                              and share the group base
+// o, dout, dk_exp, dv_exp stay [s, b, hq, D] and lse, di [b, hq, s]; dq is
+// written into the q slots of a dqkv buffer of the packed geometry.  Every
+// offset is a multiple of D, so the 16-byte vector accesses stay aligned.
+//
+// Compiled through flash_attn_qkv.hip for the reason given above for the
+// varlen kernels.  Unlike those, these keep complementary-pair causal
+// scheduling: they run the flagship's shape, where dropping it costs
+// 1.5-1.8x.  dq and dkv keep the dense structure (noinline bodies, two call
+// sites); the forward inlines one copy of its body in a two-pass loop.
+// ---------------------------------------------------------------------------
+#ifdef GALV_FLASH_PACKED_TU
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wignored-attributes"
+
+struct PackedHead {
+  long q_base, kv_base, o_base, lse_base;
+  int qkv_str, o_str;
+};
+
+template <int D>
+DEV_INLINE PackedHead packed_head(int b, int s, int G, int qpg) {
+  PackedHead p;
+  const int hq = G * qpg;
+  const int bh = blockIdx.y;
+  const int bi = bh / hq;
+  const int h = bh - bi * hq;
+  const int g = h / qpg;
+  const int slot = h - g * qpg;
+  const long grp = ((long)bi * G + g) * (qpg + 2);
+  p.q_base = (grp + slot) * D;
+  p.kv_base = grp * D;
+  p.o_base = ((long)bi * hq + h) * D;
+  p.lse_base = ((long)bi * hq + h) * s;
+  p.qkv_str = b * G * (qpg + 2) * D;
+  p.o_str = b * hq * D;
+  return p;
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_packed_fwd_kernel(const __bf16* __restrict__ qkv,
+                             __bf16* __restrict__ o, float* __restrict__ lse,
+                             int b, int s, int G, int qpg, float scale,
+                             bool causal, bool paired) {
+  constexpr int KB = 64, QBF = 256;
+  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  const PackedHead p = packed_head<D>(b, s, G, qpg);
+  const __bf16* k = qkv + (long)qpg * D;
+  const __bf16* v = k + D;
+  const OutOwn oa{p.o_base, p.o_str};
+  const float sl2e = scale * 1.4426950408889634f;
+  const int nqb = (s + QBF - 1) / QBF;
+  // one inlined copy of the body, run for the block and then for its
+  // complementary partner: out of line (as in the dense kernel) the
+  // compiler serialised the V staging loads of the full-tile path here
+  for (int pass = 0; pass < 2; ++pass) {
+    const int qb = pass == 0 ? (int)blockIdx.x : nqb - 1 - (int)blockIdx.x;
+    if (pass == 1) {
+      if (!(causal && paired && qb > (int)blockIdx.x)) break;
+      __syncthreads();
+    }
+    [[clang::always_inline]] flash_fwd_block<D, false, false, OutOwn>(
+        qb, qkv, k, v, o, lse, smem, p.q_base, p.kv_base, p.lse_base,
+        p.qkv_str, p.qkv_str, 0, s, s, sl2e, causal, nullptr, 0, 0, oa);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_packed_bwd_dq_kernel(const __bf16* __restrict__ dout,
+                                const __bf16* __restrict__ qkv,
+                                const float* __restrict__ lse,
+                                const float* __restrict__ di,
+                                __bf16* __restrict__ dqkv, int b, int s,
+                                int G, int qpg, float scale, bool causal,
+                                bool paired) {
+  constexpr int KB = 32, QBF = 256;
+  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  const PackedHead p = packed_head<D>(b, s, G, qpg);
+  const __bf16* k = qkv + (long)qpg * D;
+  const __bf16* v = k + D;
+  const OutOwn oa{p.o_base, p.o_str};
+  const int nqb = (s + QBF - 1) / QBF;
+  flash_bwd_dq_block<D, false, false, OutOwn>(
+      blockIdx.x, dout, qkv, k, v, lse, di, dqkv, smem, p.q_base, p.kv_base,
+      p.lse_base, p.qkv_str, p.qkv_str, 0, s, s, scale, causal, nullptr, 0,
+      0, oa);
+  const int qb2 = nqb - 1 - (int)blockIdx.x;
+  if (causal && paired && qb2 > (int)blockIdx.x) {
+    __syncthreads();
+    flash_bwd_dq_block<D, false, false, OutOwn>(
+        qb2, dout, qkv, k, v, lse, di, dqkv, smem, p.q_base, p.kv_base,
+        p.lse_base, p.qkv_str, p.qkv_str, 0, s, s, scale, causal, nullptr,
+        0, 0, oa);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_packed_bwd_dkv_kernel(const __bf16* __restrict__ dout,
+                                 const __bf16* __restrict__ qkv,
+                                 const float* __restrict__ lse,
+                                 const float* __restrict__ di,
+                                 __bf16* __restrict__ dk_exp,  // [s,b,hq,D]
+                                 __bf16* __restrict__ dv_exp, int b, int s,
+                                 int G, int qpg, float scale, bool causal,
+                                 bool paired) {
+  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
+  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  __shared__ __align__(16) float lsedi[4 * QT];
+  const PackedHead p = packed_head<D>(b, s, G, qpg);
+  const __bf16* k = qkv + (long)qpg * D;
+  const __bf16* v = k + D;
+  const OutOwn oa{p.o_base, p.o_str};
+  const int nkb = (s + KBW - 1) / KBW;
+  // dk_exp / dv_exp carry hq heads in o's layout
+  flash_bwd_dkv_block<D, false, false, OutOwn>(
+      blockIdx.x, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
+      p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
+      p.o_str, 0, s, s, scale, causal, nullptr, nullptr, 0, 0, oa);
+  const int kb2 = nkb - 1 - (int)blockIdx.x;
+  if (causal && paired && kb2 > (int)blockIdx.x) {
+    __syncthreads();
+    flash_bwd_dkv_block<D, false, false, OutOwn>(
+        kb2, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
+        p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
+        p.o_str, 0, s, s, scale, causal, nullptr, nullptr, 0, 0, oa);
+  }
+}
+
+#pragma clang diagnostic pop
+#endif  // GALV_FLASH_PACKED_TU
+
+// ---------------------------------------------------------------------------
 // MFMA layout probe: one-wave 32x32x16 GEMM from global memory laid out by
 // the assumed fragment maps. Validated against torch matmul on-device.
 // ---------------------------------------------------------------------------
@@ -1230,7 +1402,7 @@ __global__ void mfma_probe_kernel(const __bf16* __restrict__ A,  // [32][16]
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-#ifndef GALV_FLASH_VARLEN_TU
+#if !defined(GALV_FLASH_VARLEN_TU) && !defined(GALV_FLASH_PACKED_TU)
 template <int D>
 static void flash_fwd_launch_d(const __bf16* q, const __bf16* k,
                                const __bf16* v, __bf16* o, float* lse, int b,
@@ -1349,7 +1521,7 @@ void mfma_probe_launch(const __bf16* A, const __bf16* B, float* Dst, bool alt,
                        A, B, Dst);
 }
 
-#else  // GALV_FLASH_VARLEN_TU
+#elif defined(GALV_FLASH_VARLEN_TU)
 
 // varlen: grid.x covers the longest segment, grid.y = (segment, head)
 template <int D>
@@ -1413,4 +1585,64 @@ void flash_varlen_bwd_launch(const __bf16* dout, const __bf16* q,
                                    hkv, scale, causal, sbhd, st);
 }
 
-#endif  // GALV_FLASH_VARLEN_TU
+#else  // GALV_FLASH_PACKED_TU
+
+// packed QKV: the dense grids (and their underfill-aware pairing rule) with
+// hq = G*qpg heads
+template <int D>
+static void flash_packed_fwd_launch_d(const __bf16* qkv, __bf16* o,
+                                      float* lse, int b, int s, int G,
+                                      int qpg, float scale, bool causal,
+                                      hipStream_t st) {
+  const int hq = G * qpg;
+  const int nqb = (s + 255) / 256;
+  const bool paired = causal && ((nqb + 1) / 2) * (long)b * hq >= 256;
+  dim3 grid(paired ? (nqb + 1) / 2 : nqb, b * hq);
+  hipLaunchKernelGGL((flash_packed_fwd_kernel<D>), grid, dim3(512), 0, st,
+                     qkv, o, lse, b, s, G, qpg, scale, causal, paired);
+}
+
+void flash_packed_fwd_launch(const __bf16* qkv, __bf16* o, float* lse, int b,
+                             int s, int G, int qpg, int d, float scale,
+                             bool causal, hipStream_t st) {
+  if (d == 64)
+    flash_packed_fwd_launch_d<64>(qkv, o, lse, b, s, G, qpg, scale, causal,
+                                  st);
+  else
+    flash_packed_fwd_launch_d<128>(qkv, o, lse, b, s, G, qpg, scale, causal,
+                                   st);
+}
+
+template <int D>
+static void flash_packed_bwd_launch_d(const __bf16* dout, const __bf16* qkv,
+                                      const float* lse, const float* di,
+                                      __bf16* dqkv, __bf16* dk_exp,
+                                      __bf16* dv_exp, int b, int s, int G,
+                                      int qpg, float scale, bool causal,
+                                      hipStream_t st) {
+  const int hq = G * qpg;
+  const int nb = (s + 255) / 256;  // q blocks == key blocks (sq == skv)
+  const bool paired = causal && ((nb + 1) / 2) * (long)b * hq >= 256;
+  dim3 grid(paired ? (nb + 1) / 2 : nb, b * hq);
+  hipLaunchKernelGGL((flash_packed_bwd_dq_kernel<D>), grid, dim3(512), 0, st,
+                     dout, qkv, lse, di, dqkv, b, s, G, qpg, scale, causal,
+                     paired);
+  hipLaunchKernelGGL((flash_packed_bwd_dkv_kernel<D>), grid, dim3(512), 0,
+                     st, dout, qkv, lse, di, dk_exp, dv_exp, b, s, G, qpg,
+                     scale, causal, paired);
+}
+
+void flash_packed_bwd_launch(const __bf16* dout, const __bf16* qkv,
+                             const float* lse, const float* di, __bf16* dqkv,
+                             __bf16* dk_exp, __bf16* dv_exp, int b, int s,
+                             int G, int qpg, int d, float scale, bool causal,
+                             hipStream_t st) {
+  if (d == 64)
+    flash_packed_bwd_launch_d<64>(dout, qkv, lse, di, dqkv, dk_exp, dv_exp,
+                                  b, s, G, qpg, scale, causal, st);
+  else
+    flash_packed_bwd_launch_d<128>(dout, qkv, lse, di, dqkv, dk_exp, dv_exp,
+                                   b, s, G, qpg, scale, causal, st);
+}
+
+#endif  // TU selection

@@ -1,0 +1,6 @@
+// Packed-QKV flash attention: the flash_packed_* kernels and launchers of
+// flash_attn.hip, compiled as a module of their own so that the dense
+// kernels' code objects are not perturbed (see the notes above
+// flash_varlen_fwd_kernel and flash_packed_fwd_kernel in flash_attn.hip).
+#define GALV_FLASH_PACKED_TU
+#include "flash_attn.hip"

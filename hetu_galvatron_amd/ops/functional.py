@@ -286,6 +286,100 @@ def flash_attention_varlen(q, k, v, cu_seqlens, max_seqlen: int,
     return (o, lse) if return_lse else o
 
 
+class _FusedQKVAttention(torch.autograd.Function):
+    """RoPE + flash attention on the packed linear_qkv output, native only.
+    q, k and v are never separated in memory: RoPE rotates the q and k
+    slots in place, the packed flash kernels address the slots directly, and
+    one finishing kernel turns dqkv into the gradient of the packed buffer
+    (inverse rotation + GQA group sum).  ops/csrc/flash_attn.hip (packed
+    section), elementwise.hip (rope_qkv_kernel, qkv_grad_finish_kernel)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, geom, causal, scale):
+        ext = get_ext(False)
+        # qkv is rewritten in place: tell autograd, so that a producer that
+        # saved this buffer for its own backward fails loudly instead of
+        # reading rotated values.  A dirty input has to be returned.
+        ctx.mark_dirty(qkv)
+        ctx.set_materialize_grads(False)
+        packed = qkv.view(*geom)
+        if cos is not None:
+            ext.rope_qkv_(packed, cos, sin)
+        o, lse = ext.flash_attn_qkv_fwd(packed, causal, scale)
+        # the rotated buffer is what backward needs: nothing else is kept
+        ctx.save_for_backward(qkv, o, lse, cos, sin)
+        ctx.geom = geom
+        ctx.causal = causal
+        ctx.scale = scale
+        return o, qkv
+
+    @staticmethod
+    def backward(ctx, do, _dbuf):
+        if do is None:
+            return None, None, None, None, None, None
+        qkv, o, lse, cos, sin = ctx.saved_tensors
+        ext = get_ext(False)
+        dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_bwd(
+            do.contiguous(), qkv.view(*ctx.geom), o, lse, ctx.causal,
+            ctx.scale)
+        ext.qkv_grad_finish_(dqkv, dk_exp, dv_exp, cos, sin)
+        return dqkv.view(qkv.shape), None, None, None, None, None
+
+
+def fused_qkv_attention_native(qkv, d, cos, window=None) -> bool:
+    """True when fused_qkv_attention runs the packed HIP kernels (bf16 on
+    the GPU, head dim 64|128, cos None or [s, d/2], no effective window)."""
+    return (use_native(qkv) and qkv.dtype == torch.bfloat16
+            and d in (64, 128)
+            and (cos is None or cos.dim() == 2)
+            and (window is None or window >= qkv.shape[0]))
+
+
+def fused_qkv_attention(qkv, cos, sin, num_groups: int, q_per_group: int,
+                        causal: bool = True,
+                        softmax_scale: Optional[float] = None,
+                        window: Optional[int] = None):
+    """Self-attention straight from the linear_qkv output.
+
+    qkv: [s, b, num_groups*(q_per_group+2)*d] (or already viewed
+    [s, b, G, qpg+2, d]), interleaved by kv group: q heads in slots
+    0..qpg-1, k in slot qpg, v in slot qpg+1.  cos/sin: [s, d/2] NEOX
+    tables, or None for no rotary embedding.  Returns o [s, b, G*qpg, d].
+
+    The native path CONSUMES qkv: RoPE rotates it in place (marked dirty
+    for autograd), so the caller must not use it afterwards, its producer
+    must not have saved it for backward, and it cannot be a leaf that
+    requires grad.  Everything else (CPU, fp32, other head dims, per-row
+    tables, an effective sliding window) runs the composition of slice,
+    apply_rope and flash_attention and leaves qkv alone."""
+    s, b = qkv.shape[0], qkv.shape[1]
+    d = qkv.shape[2:].numel() // (num_groups * (q_per_group + 2))
+    geom = (s, b, num_groups, q_per_group + 2, d)
+    scale = softmax_scale if softmax_scale is not None \
+        else 1.0 / math.sqrt(d)
+    if fused_qkv_attention_native(qkv, d, cos, window):
+        if cos is not None:
+            cos = cos[:s].contiguous().float()
+            sin = sin[:s].contiguous().float()
+        # the buffer itself goes in, not a view of it: an in-place op on a
+        # view would make autograd copy the whole gradient back into the base
+        o, _ = _FusedQKVAttention.apply(qkv.contiguous(), cos, sin, geom,
+                                        causal, scale)
+        return o
+    qkv = qkv.view(*geom)
+    q = qkv[:, :, :, :q_per_group].reshape(s, b, -1, d)
+    k = qkv[:, :, :, q_per_group].reshape(s, b, -1, d)
+    v = qkv[:, :, :, q_per_group + 1].reshape(s, b, -1, d)
+    q, k = q.contiguous(), k.contiguous()
+    if cos is not None:
+        if cos.dim() != 2:
+            raise ValueError("fused_qkv_attention: cos/sin must be [s, d/2]")
+        q, k = apply_rope(q, cos, sin), apply_rope(k, cos, sin)
+    return flash_attention(q, k, v.contiguous(), causal=causal,
+                           softmax_scale=softmax_scale, window=window,
+                           sbhd=True)
+
+
 class _FlashBiasAttention(torch.autograd.Function):
     """Biased flash attention (t5 relative bias [hq, sq, skv]) with grads
     for q/k/v AND the bias (dbias batch-summed, flows back into the bias

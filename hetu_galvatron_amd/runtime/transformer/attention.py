@@ -29,6 +29,7 @@ from .attention_impl import (
     flash_bias_attention, local_attention,
 )
 from .rope import apply_rope_qk
+from ...ops import fused_qkv_attention
 
 
 def _dropout_attention(q, k, v, causal, scale, p):
@@ -127,6 +128,9 @@ class SelfAttention(nn.Module):
             self.core_attention = inner
         else:
             self.core_attention = None  # plain local flash
+        # plain local path only: ops.fused_qkv_attention on the packed
+        # linear_qkv output (off = split, apply_rope, flash_attention)
+        self.fused_qkv = True
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                 attn_bias: torch.Tensor = None, cu_seqlens=None,
@@ -142,6 +146,19 @@ class SelfAttention(nn.Module):
         over the global kv axis."""
         qkv = self.linear_qkv(x)  # [s, b, (hq_l + 2*hkv_l)*d]
         s, b = qkv.shape[0], qkv.shape[1]
+        if self.fused_qkv and self.core_attention is None \
+                and attn_bias is None and cu_seqlens is None \
+                and self.q_layernorm is None \
+                and not (self.attn_dropout > 0 and self.training) \
+                and not self.rope_interleaved \
+                and (cos is None or cos.dim() == 2):
+            # plain local path: RoPE and flash attention run on the packed
+            # buffer (consumed: linear_qkv keeps no reference to its output)
+            o = fused_qkv_attention(
+                qkv, cos, sin, self.num_groups_local, self.q_per_group,
+                causal=self.causal, softmax_scale=self.softmax_scale,
+                window=self.window)
+            return self.linear_proj(o.reshape(s, b, -1))
         qkv = qkv.view(s, b, self.num_groups_local, self.q_per_group + 2,
                        self.head_dim)
         q = qkv[:, :, :, : self.q_per_group].reshape(s, b, -1, self.head_dim)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -112,6 +112,55 @@ def bench_varlen(iters, repeats=9, dense_only=False):
             nseg * L * (L + 1) / 2)
 
 
+def bench_qkv(iters, repeats=9):
+    """linear_qkv output -> attention output, forward + backward, one
+    layer-microbatch of the llama-3-8b bench (b4 s4096 h32/8 d128 causal
+    bf16, packed buffer [s, b, 8, 6, 128]):
+      composition   slice q/k/v, apply_rope x2, flash_attention(sbhd) and
+                    autograd's backward of all of it
+      fused         ops.fused_qkv_attention (in-place packed RoPE, packed
+                    flash kernels, one finishing kernel)
+    The fused op consumes its input (rotated in place, so not a leaf): both
+    rows start from a fresh x.clone(), which stands for the producer and
+    costs both the same."""
+    from hetu_galvatron_amd.ops import (apply_rope, flash_attention,
+                                        fused_qkv_attention)
+    from hetu_galvatron_amd.ops.reference_ops import rope_freqs
+    s, b, G, qpg, d = 4096, 4, 8, 4, 128
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randn(s, b, G, qpg + 2, d, device="cuda",
+                    generator=g).bfloat16().requires_grad_(True)
+    do = torch.randn(s, b, G * qpg, d, device="cuda", generator=g).bfloat16()
+    cos, sin = rope_freqs(s, d, device="cuda")
+
+    def composition():
+        xc = x.clone()
+        q = xc[:, :, :, :qpg].reshape(s, b, -1, d)
+        k = xc[:, :, :, qpg].reshape(s, b, -1, d)
+        v = xc[:, :, :, qpg + 1].reshape(s, b, -1, d)
+        q = apply_rope(q.contiguous(), cos, sin)
+        k = apply_rope(k.contiguous(), cos, sin)
+        return flash_attention(q, k, v.contiguous(), causal=True, sbhd=True)
+
+    def fused():
+        return fused_qkv_attention(x.clone(), cos, sin, G, qpg, causal=True)
+
+    def fwd_bwd(fn):
+        def run():
+            x.grad = None
+            fn().backward(do)
+        return run
+
+    for name, fn in (("composition", composition), ("fused", fused)):
+        with torch.no_grad():
+            tf, lo, hi = median_of_windows(fn, iters, repeats)
+        print(f"qkv {name:12s} fwd     {tf*1e3:7.3f} ms "
+              f"[{lo*1e3:.3f}, {hi*1e3:.3f}]")
+        tb, lo, hi = median_of_windows(fwd_bwd(fn), iters, repeats)
+        print(f"qkv {name:12s} fwd+bwd {tb*1e3:7.3f} ms "
+              f"[{lo*1e3:.3f}, {hi*1e3:.3f}]")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -194,7 +243,7 @@ def main():
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=9,
-                    help="timed windows per row (varlen entry)")
+                    help="timed windows per row (varlen and qkv entries)")
     ap.add_argument("--dense-only", action="store_true",
                     help="varlen entry: time only the dense kernels")
     args = ap.parse_args()
@@ -203,7 +252,8 @@ def main():
            "elementwise": bench_elementwise, "adam": bench_adam,
            "bias": bench_bias,
            "varlen": lambda it: bench_varlen(it, args.repeats,
-                                             args.dense_only)}
+                                             args.dense_only),
+           "qkv": lambda it: bench_qkv(it, args.repeats)}
     if args.what == "all":
         for f in fns.values():
             f(args.iters)
