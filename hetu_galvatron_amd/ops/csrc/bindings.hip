@@ -83,15 +83,56 @@ __bf16* bfp_mut(Tensor& t) {
 
 bool is_bf16(const Tensor& t) { return t.scalar_type() == at::kBFloat16; }
 
+// The kernels read bf16 or fp32 and nothing else: any other dtype (fp16,
+// fp64, integers) is refused here by name, never reinterpreted.
+#define CHECK_IN(t, who)                                                     \
+  TORCH_CHECK((t).is_cuda() && (t).is_contiguous() &&                        \
+                  ((t).scalar_type() == at::kBFloat16 ||                     \
+                   (t).scalar_type() == at::kFloat),                         \
+              who ": " #t " must be a contiguous bf16 or fp32 GPU tensor, "  \
+              "got ", (t).scalar_type(), " on ", (t).device())
+// t: same dtype, device and shape as x
+#define CHECK_LIKE(t, x, who)                                                \
+  TORCH_CHECK((t).is_cuda() && (t).is_contiguous() &&                        \
+                  (t).scalar_type() == (x).scalar_type() &&                  \
+                  (t).device() == (x).device() && (t).sizes() == (x).sizes(), \
+              who ": " #t " must be contiguous with " #x "'s dtype, device " \
+              "and shape ", (x).sizes(), ", got ", (t).scalar_type(), " ",   \
+              (t).sizes())
+// t: a per-column vector (norm weight / bias) with x's dtype and H elements
+#define CHECK_VEC(t, x, H, who)                                              \
+  TORCH_CHECK((t).is_cuda() && (t).is_contiguous() &&                        \
+                  (t).scalar_type() == (x).scalar_type() &&                  \
+                  (t).device() == (x).device() && (t).numel() == (H),        \
+              who ": " #t " must be contiguous with " #x "'s dtype and "     \
+              "device and ", (H), " elements, got ", (t).scalar_type(), " ", \
+              (t).sizes())
+// t: a per-row fp32 statistic saved by the forward (n elements)
+#define CHECK_STAT(t, x, n, who)                                             \
+  TORCH_CHECK((t).is_cuda() && (t).scalar_type() == at::kFloat &&            \
+                  (t).device() == (x).device() && (t).numel() == (n),        \
+              who ": " #t " must be fp32 on " #x "'s device with ", (n),     \
+              " elements, got ", (t).scalar_type(), " ", (t).sizes())
+#define CHECK_NORM_H(H, who)                                                 \
+  TORCH_CHECK((H) > 0 && (H) % 8 == 0 && (H) <= 16384,                       \
+              who ": H must be %8, <=16k")
+
 // ---- norms ----------------------------------------------------------------
 std::tuple<Tensor, Tensor> rmsnorm_fwd(const Tensor& x, const Tensor& w,
                                        double eps) {
-  CHECK_GPU(x);
+  CHECK_IN(x, "rmsnorm_fwd");
+  TORCH_CHECK(x.dim() >= 1, "rmsnorm_fwd: x must have a last dim");
   const int H = x.size(-1);
+  CHECK_NORM_H(H, "rmsnorm");
   const long n = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0 && H <= 16384, "rmsnorm: H must be %8, <=16k");
+  CHECK_VEC(w, x, H, "rmsnorm_fwd");
   auto y = at::empty_like(x);
   auto invrms = at::empty({n}, x.options().dtype(at::kFloat));
+  if (n == 0) {
+    auto sz = x.sizes().vec();
+    sz.pop_back();
+    return {y, invrms.view(sz)};
+  }
   if (is_bf16(x))
     rmsnorm_fwd_launch_t<__bf16>(bfp(x), bfp(w), bfp_mut(y),
                                  invrms.data_ptr<float>(), n, H, (float)eps,
@@ -107,11 +148,17 @@ std::tuple<Tensor, Tensor> rmsnorm_fwd(const Tensor& x, const Tensor& w,
 
 std::tuple<Tensor, Tensor> rmsnorm_bwd(const Tensor& dy, const Tensor& x,
                                        const Tensor& w, const Tensor& invrms) {
-  CHECK_GPU(dy);
+  CHECK_IN(x, "rmsnorm_bwd");
+  TORCH_CHECK(x.dim() >= 1, "rmsnorm_bwd: x must have a last dim");
   const int H = x.size(-1);
+  CHECK_NORM_H(H, "rmsnorm");
   const long n = x.numel() / H;
+  CHECK_LIKE(dy, x, "rmsnorm_bwd");
+  CHECK_VEC(w, x, H, "rmsnorm_bwd");
+  CHECK_STAT(invrms, x, n, "rmsnorm_bwd");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
+  if (n == 0) return {dx, dw};
   const int G = norm_bwd_grid(n);
   auto dw_part = at::empty({G, H}, x.options().dtype(at::kFloat));
   auto inv = invrms.contiguous();
@@ -134,14 +181,23 @@ std::tuple<Tensor, Tensor, Tensor> add_rmsnorm_fwd(const Tensor& x,
                                                    const Tensor& res,
                                                    const Tensor& w,
                                                    double eps) {
-  CHECK_GPU(x); CHECK_GPU(res);
-  TORCH_CHECK(is_bf16(x) && is_bf16(res), "add_rmsnorm: bf16 only");
+  CHECK_IN(x, "add_rmsnorm_fwd");
+  TORCH_CHECK(is_bf16(x), "add_rmsnorm_fwd: x must be bf16 (bf16 only), got ",
+              x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1, "add_rmsnorm_fwd: x must have a last dim");
   const int H = x.size(-1);
+  CHECK_NORM_H(H, "rmsnorm");
   const long n = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0 && H <= 16384, "rmsnorm: H must be %8, <=16k");
+  CHECK_LIKE(res, x, "add_rmsnorm_fwd");
+  CHECK_VEC(w, x, H, "add_rmsnorm_fwd");
   auto y = at::empty_like(x);
   auto sum = at::empty_like(x);
   auto invrms = at::empty({n}, x.options().dtype(at::kFloat));
+  if (n == 0) {
+    auto sz = x.sizes().vec();
+    sz.pop_back();
+    return {y, sum, invrms.view(sz)};
+  }
   rmsnorm_fwd_launch_t<__bf16>(bfp(x), bfp(w), bfp_mut(y),
                                invrms.data_ptr<float>(), n, H, (float)eps,
                                cur_stream(), bfp(res), bfp_mut(sum));
@@ -157,11 +213,20 @@ std::tuple<Tensor, Tensor> add_rmsnorm_bwd(const Tensor& dy,
                                            const Tensor& sum,
                                            const Tensor& w,
                                            const Tensor& invrms) {
-  CHECK_GPU(dy);
+  CHECK_IN(sum, "add_rmsnorm_bwd");
+  TORCH_CHECK(is_bf16(sum), "add_rmsnorm_bwd: sum must be bf16 (bf16 only), "
+              "got ", sum.scalar_type());
+  TORCH_CHECK(sum.dim() >= 1, "add_rmsnorm_bwd: sum must have a last dim");
   const int H = sum.size(-1);
+  CHECK_NORM_H(H, "rmsnorm");
   const long n = sum.numel() / H;
+  CHECK_LIKE(dy, sum, "add_rmsnorm_bwd");
+  CHECK_LIKE(dsum, sum, "add_rmsnorm_bwd");
+  CHECK_VEC(w, sum, H, "add_rmsnorm_bwd");
+  CHECK_STAT(invrms, sum, n, "add_rmsnorm_bwd");
   auto dx = at::empty_like(sum);
   auto dw = at::zeros({H}, sum.options().dtype(at::kFloat));
+  if (n == 0) return {dx, dw};
   const int G = norm_bwd_grid(n);
   auto dw_part = at::empty({G, H}, sum.options().dtype(at::kFloat));
   auto inv = invrms.contiguous();
@@ -176,13 +241,21 @@ std::tuple<Tensor, Tensor> add_rmsnorm_bwd(const Tensor& dy,
 std::tuple<Tensor, Tensor, Tensor> layernorm_fwd(const Tensor& x,
                                                  const Tensor& w,
                                                  const Tensor& b, double eps) {
-  CHECK_GPU(x);
+  CHECK_IN(x, "layernorm_fwd");
+  TORCH_CHECK(x.dim() >= 1, "layernorm_fwd: x must have a last dim");
   const int H = x.size(-1);
+  CHECK_NORM_H(H, "layernorm");
   const long n = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0 && H <= 16384, "layernorm: H must be %8, <=16k");
+  CHECK_VEC(w, x, H, "layernorm_fwd");
+  CHECK_VEC(b, x, H, "layernorm_fwd");
   auto y = at::empty_like(x);
   auto mean = at::empty({n}, x.options().dtype(at::kFloat));
   auto invstd = at::empty({n}, x.options().dtype(at::kFloat));
+  if (n == 0) {
+    auto sz = x.sizes().vec();
+    sz.pop_back();
+    return {y, mean.view(sz), invstd.view(sz)};
+  }
   if (is_bf16(x))
     layernorm_fwd_launch_t<__bf16>(bfp(x), bfp(w), bfp(b), bfp_mut(y),
                                    mean.data_ptr<float>(),
@@ -203,11 +276,18 @@ std::tuple<Tensor, Tensor, Tensor> layernorm_bwd(const Tensor& dy,
                                                  const Tensor& w,
                                                  const Tensor& mean,
                                                  const Tensor& invstd) {
-  CHECK_GPU(dy);
+  CHECK_IN(x, "layernorm_bwd");
+  TORCH_CHECK(x.dim() >= 1, "layernorm_bwd: x must have a last dim");
   const int H = x.size(-1);
+  CHECK_NORM_H(H, "layernorm");
   const long n = x.numel() / H;
+  CHECK_LIKE(dy, x, "layernorm_bwd");
+  CHECK_VEC(w, x, H, "layernorm_bwd");
+  CHECK_STAT(mean, x, n, "layernorm_bwd");
+  CHECK_STAT(invstd, x, n, "layernorm_bwd");
   auto dx = at::empty_like(x);
   auto dwdb = at::zeros({2, H}, x.options().dtype(at::kFloat));
+  if (n == 0) return {dx, dwdb[0], dwdb[1]};
   const int G = norm_bwd_grid(n);
   auto part = at::empty({2, G, H}, x.options().dtype(at::kFloat));
   auto m = mean.contiguous(), r = invstd.contiguous();
@@ -227,14 +307,16 @@ std::tuple<Tensor, Tensor, Tensor> layernorm_bwd(const Tensor& dy,
 
 // ---- swiglu / rope --------------------------------------------------------
 Tensor swiglu_fwd(const Tensor& x) {
-  CHECK_GPU(x);
+  CHECK_IN(x, "swiglu_fwd");
+  TORCH_CHECK(x.dim() >= 1, "swiglu_fwd: x must have a last dim");
   const int F2 = x.size(-1);
-  TORCH_CHECK(F2 % 16 == 0, "swiglu: last dim must be %16");
+  TORCH_CHECK(F2 > 0 && F2 % 16 == 0, "swiglu: last dim must be %16");
   const int F = F2 / 2;
   const long rows = x.numel() / F2;
   auto sizes = x.sizes().vec();
   sizes.back() = F;
   auto y = at::empty(sizes, x.options());
+  if (rows == 0) return y;
   if (is_bf16(x))
     swiglu_fwd_launch_t<__bf16>(bfp(x), bfp_mut(y), rows, F, cur_stream());
   else
@@ -244,11 +326,22 @@ Tensor swiglu_fwd(const Tensor& x) {
 }
 
 Tensor swiglu_bwd(const Tensor& dy, const Tensor& x) {
-  CHECK_GPU(dy);
+  CHECK_IN(x, "swiglu_bwd");
+  TORCH_CHECK(x.dim() >= 1, "swiglu_bwd: x must have a last dim");
   const int F2 = x.size(-1);
+  TORCH_CHECK(F2 > 0 && F2 % 16 == 0, "swiglu: last dim must be %16");
   const int F = F2 / 2;
   const long rows = x.numel() / F2;
+  auto want = x.sizes().vec();
+  want.back() = F;
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
+                  dy.scalar_type() == x.scalar_type() &&
+                  dy.device() == x.device() && dy.sizes() == at::IntArrayRef(want),
+              "swiglu_bwd: dy must be contiguous with x's dtype and device "
+              "and shape ", at::IntArrayRef(want), " (x's with the last dim "
+              "halved), got ", dy.scalar_type(), " ", dy.sizes());
   auto dx = at::empty_like(x);
+  if (rows == 0) return dx;
   if (is_bf16(x))
     swiglu_bwd_launch_t<__bf16>(bfp(dy), bfp(x), bfp_mut(dx), rows, F,
                                 cur_stream());
@@ -260,15 +353,32 @@ Tensor swiglu_bwd(const Tensor& dy, const Tensor& x) {
 
 Tensor rope_fwd(const Tensor& x, const Tensor& cos_t, const Tensor& sin_t,
                 bool conj) {
-  CHECK_GPU(x);
+  CHECK_IN(x, "rope_fwd");
   TORCH_CHECK(x.dim() == 4, "rope: x must be [s,b,h,d]");
   const int d = x.size(3);
-  TORCH_CHECK(d % 16 == 0, "rope: head dim must be %16");
+  TORCH_CHECK(d > 0 && d % 16 == 0, "rope: head dim must be %16");
   const long rows = x.numel() / d;
   const int bh = x.size(1) * x.size(2);
+  // the kernel reads table row s_idx for every s_idx < s and d/2 columns
+  // of it: a shorter or narrower table would be read out of bounds
+  TORCH_CHECK(cos_t.is_cuda() && cos_t.device() == x.device() &&
+                  cos_t.is_floating_point() && cos_t.dim() == 2 &&
+                  cos_t.size(0) >= x.size(0) && cos_t.size(1) * 2 == d,
+              "rope_fwd: cos_t must be a floating [>=s, d/2] = [>=",
+              x.size(0), ", ", d / 2, "] table on x's device, got ",
+              cos_t.scalar_type(), " ", cos_t.sizes(), " on ",
+              cos_t.device());
+  TORCH_CHECK(sin_t.is_cuda() && sin_t.device() == x.device() &&
+                  sin_t.is_floating_point() &&
+                  sin_t.sizes() == cos_t.sizes(),
+              "rope_fwd: sin_t must be a floating table on x's device "
+              "shaped like cos_t ", cos_t.sizes(), ", got ",
+              sin_t.scalar_type(), " ", sin_t.sizes(), " on ",
+              sin_t.device());
   auto c = cos_t.contiguous().to(at::kFloat);
   auto s = sin_t.contiguous().to(at::kFloat);
   auto y = at::empty_like(x);
+  if (rows == 0) return y;
   if (is_bf16(x))
     rope_launch_t<__bf16>(bfp(x), bfp_mut(y), c.data_ptr<float>(),
                           s.data_ptr<float>(), rows, bh, d, conj,
@@ -657,11 +767,26 @@ Tensor mfma_probe(const Tensor& A, const Tensor& B, bool alt) {
 }
 
 // ---- vocab-parallel CE ----------------------------------------------------
+// logits [n, V] bf16|fp32 with V >= 1; target int64 [n]; per-row stats fp32 [n]
+#define CHECK_CE_LOGITS(logits, who)                                        \
+  CHECK_IN(logits, who);                                                    \
+  TORCH_CHECK((logits).dim() >= 1 && (logits).size(-1) >= 1,                \
+              who ": logits must be [n, V] with V >= 1, got ",              \
+              (logits).sizes())
+#define CHECK_CE_TARGET(target, logits, n, who)                             \
+  TORCH_CHECK((target).is_cuda() && (target).scalar_type() == at::kLong &&  \
+                  (target).device() == (logits).device() &&                 \
+                  (target).numel() == (n),                                  \
+              who ": target must be int64 on logits' device with ", (n),    \
+              " elements, got ", (target).scalar_type(), " ",               \
+              (target).sizes())
+
 Tensor ce_max(const Tensor& logits) {
-  CHECK_GPU(logits);
+  CHECK_CE_LOGITS(logits, "ce_max");
   const long V = logits.size(-1);
   const long n = logits.numel() / V;
   auto out = at::empty({n}, logits.options().dtype(at::kFloat));
+  if (n == 0) return out;
   if (is_bf16(logits))
     ce_max_launch_t<__bf16>(bfp(logits), out.data_ptr<float>(), n, V,
                             cur_stream());
@@ -675,13 +800,16 @@ std::tuple<Tensor, Tensor> ce_sum_target(const Tensor& logits,
                                          const Tensor& target,
                                          const Tensor& gmax,
                                          long vocab_start) {
-  CHECK_GPU(logits);
+  CHECK_CE_LOGITS(logits, "ce_sum_target");
   const long V = logits.size(-1);
   const long n = logits.numel() / V;
+  CHECK_CE_TARGET(target, logits, n, "ce_sum_target");
+  CHECK_STAT(gmax, logits, n, "ce_sum_target");
   auto t = target.contiguous();
   auto g = gmax.contiguous();
   auto sumexp = at::empty({n}, logits.options().dtype(at::kFloat));
   auto tlogit = at::empty({n}, logits.options().dtype(at::kFloat));
+  if (n == 0) return {sumexp, tlogit};
   if (is_bf16(logits))
     ce_sum_target_launch_t<__bf16>(bfp(logits), t.data_ptr<long>(),
                                    g.data_ptr<float>(),
@@ -699,9 +827,18 @@ std::tuple<Tensor, Tensor> ce_sum_target(const Tensor& logits,
 
 Tensor ce_bwd(Tensor logits, const Tensor& target, const Tensor& gmax,
               const Tensor& sumexp, const Tensor& grad_out, long vocab_start) {
-  CHECK_GPU(logits);
+  CHECK_CE_LOGITS(logits, "ce_bwd");
   const long V = logits.size(-1);
   const long n = logits.numel() / V;
+  CHECK_CE_TARGET(target, logits, n, "ce_bwd");
+  CHECK_STAT(gmax, logits, n, "ce_bwd");
+  CHECK_STAT(sumexp, logits, n, "ce_bwd");
+  TORCH_CHECK(grad_out.is_cuda() && grad_out.device() == logits.device() &&
+                  grad_out.is_floating_point() && grad_out.numel() == n,
+              "ce_bwd: grad_out must be a floating tensor on logits' device "
+              "with ", n, " elements, got ", grad_out.scalar_type(), " ",
+              grad_out.sizes());
+  if (n == 0) return logits;
   auto t = target.contiguous();
   auto g = gmax.contiguous();
   auto se = sumexp.contiguous();

@@ -211,11 +211,25 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
       if (c < H) {
         VecIO<T>::load(xv[p], xr + c);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { s += xv[p][i]; ss += xv[p][i] * xv[p][i]; }
+        for (int i = 0; i < 8; ++i) s += xv[p][i];
       }
     }
     const float mean = block_sum_256(s, red) / H;
-    const float var = block_sum_256(ss, red) / H - mean * mean;
+    // centred second pass over the registers: E[x^2] - mean^2 in fp32
+    // cancels catastrophically for rows with |mean| >> std (mean 64,
+    // std 0.05 lost 10-26 % of the variance and could go negative)
+#pragma unroll
+    for (int p = 0; p < VPT; ++p) {
+      int c = (tid + p * 256) * 8;
+      if (c < H) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float dlt = xv[p][i] - mean;
+          ss += dlt * dlt;
+        }
+      }
+    }
+    const float var = block_sum_256(ss, red) / H;
     const float inv = rsqrtf(var + eps);
     if (tid == 0) { mean_out[row] = mean; invstd_out[row] = inv; }
 #pragma unroll

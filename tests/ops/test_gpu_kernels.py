@@ -503,7 +503,8 @@ def test_moe_permute_unpermute():
     n, h, E, k = 64, 128, 4, 2
     x = torch.randn(n, h, device=dev()).bfloat16().requires_grad_(True)
     idx = torch.randint(0, E, (n, k), device=dev())
-    probs = torch.softmax(torch.randn(n, k, device=dev()), -1).reshape(-1)
+    probs = torch.softmax(torch.randn(n, k, device=dev()), -1).reshape(-1) \
+        .requires_grad_(True)
     flat = idx.reshape(-1)
     order = torch.argsort(flat, stable=True)
     rows = order // k
@@ -513,15 +514,19 @@ def test_moe_permute_unpermute():
     out = moe_unpermute(perm, p_sorted, order, n, k)
     # reference (pure torch)
     x2 = x.detach().clone().requires_grad_(True)
+    probs2 = probs.detach().clone().requires_grad_(True)
     perm2 = x2[rows]
     full = perm2.new_zeros(n * k, h)
-    full[order] = perm2 * p_sorted.unsqueeze(-1).to(perm2.dtype)
+    full[order] = perm2 * probs2[order].unsqueeze(-1).to(perm2.dtype)
     out_ref = full.reshape(n, k, h).sum(1)
     assert_close(out, out_ref, 2e-2, what="moe unpermute fwd")
     g = torch.randn_like(out)
     out.backward(g)
     out_ref.backward(g)
     assert_close(x.grad, x2.grad, 3e-2, what="moe permute/unpermute grad")
+    # dprobs, the router's gradient through the merge (the reference takes
+    # it through a bf16 product; test_gpu_kernel_edges.py compares with fp64)
+    assert_close(probs.grad, probs2.grad, 0.25, what="moe dprobs")
 
 
 # ---------------------------------------------------------------------------
