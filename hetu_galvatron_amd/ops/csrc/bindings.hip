@@ -58,6 +58,8 @@ void flash_varlen_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16
 void flash_varlen_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
 void flash_packed_fwd_launch(const __bf16*, __bf16*, float*, int, int, int, int, int, float, bool, hipStream_t);
 void flash_packed_bwd_launch(const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, float, bool, hipStream_t);
+void flash_packed_varlen_fwd_launch(const __bf16*, __bf16*, float*, const int*, int, int, int, int, int, int, int, float, bool, hipStream_t);
+void flash_packed_varlen_bwd_launch(const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, const int*, int, int, int, int, int, int, int, float, bool, hipStream_t);
 void rope_qkv_launch(__bf16*, const float*, const float*, long, int, int, int, hipStream_t);
 void qkv_grad_finish_launch(__bf16*, const __bf16*, const __bf16*, const float*, const float*, long, int, int, int, hipStream_t);
 int multi_sumsq_grid(int);
@@ -595,27 +597,35 @@ void check_qkv(const Tensor& qkv, const char* who) {
               ": b*hq exceeds the grid limit (65535)");
 }
 
-void check_rope_tables(const Tensor& qkv, const Tensor& cos_t,
-                       const Tensor& sin_t, const char* who) {
+// cos/sin: [s, d/2], or per-row [s, b, d/2] (packed documents whose
+// positions restart; rank 3 selects it, so b == 1 is not ambiguous).
+// Returns the number of consecutive kv groups that share one table row:
+// b*G for [s, d/2], G for [s, b, d/2].
+int check_rope_tables(const Tensor& qkv, const Tensor& cos_t,
+                      const Tensor& sin_t, const char* who) {
+  const bool per_row = cos_t.dim() == 3;
   TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() &&
               cos_t.scalar_type() == at::kFloat &&
               sin_t.scalar_type() == at::kFloat && cos_t.is_contiguous() &&
-              sin_t.is_contiguous() && cos_t.dim() == 2 &&
+              sin_t.is_contiguous() && (cos_t.dim() == 2 || per_row) &&
               cos_t.sizes() == sin_t.sizes() &&
               cos_t.size(0) == qkv.size(0) &&
-              cos_t.size(1) * 2 == qkv.size(4), who,
-              ": cos/sin must be contiguous fp32 [s, d/2] on the GPU");
+              (!per_row || cos_t.size(1) == qkv.size(1)) &&
+              cos_t.size(-1) * 2 == qkv.size(4), who,
+              ": cos/sin must be contiguous fp32 [s, d/2] or [s, b, d/2] "
+              "on the GPU");
+  return (int)(per_row ? qkv.size(2) : qkv.size(1) * qkv.size(2));
 }
 
 // In-place NEOX RoPE on the q and k slots; v is not touched.
 void rope_qkv_(Tensor qkv, const Tensor& cos_t, const Tensor& sin_t) {
   check_qkv(qkv, "rope_qkv_");
-  check_rope_tables(qkv, cos_t, sin_t, "rope_qkv_");
+  const int per_table_row =
+      check_rope_tables(qkv, cos_t, sin_t, "rope_qkv_");
   const long groups = qkv.size(0) * qkv.size(1) * qkv.size(2);
   rope_qkv_launch(bfp_mut(qkv), cos_t.data_ptr<float>(),
-                  sin_t.data_ptr<float>(), groups,
-                  (int)(qkv.size(1) * qkv.size(2)), (int)qkv.size(3) - 2,
-                  (int)qkv.size(4), cur_stream());
+                  sin_t.data_ptr<float>(), groups, per_table_row,
+                  (int)qkv.size(3) - 2, (int)qkv.size(4), cur_stream());
 }
 
 // -> o [s, b, hq, d], lse [b, hq, s]
@@ -682,16 +692,90 @@ void qkv_grad_finish_(Tensor dqkv, const Tensor& dk_exp, const Tensor& dv_exp,
               "qkv_grad_finish_: cos and sin go together");
   const float* cp = nullptr;
   const float* sp = nullptr;
+  int per_table_row = (int)(dqkv.size(1) * dqkv.size(2));
   if (cos_t.has_value()) {
-    check_rope_tables(dqkv, *cos_t, *sin_t, "qkv_grad_finish_");
+    per_table_row =
+        check_rope_tables(dqkv, *cos_t, *sin_t, "qkv_grad_finish_");
     cp = cos_t->data_ptr<float>();
     sp = sin_t->data_ptr<float>();
   }
   const long groups = dqkv.size(0) * dqkv.size(1) * dqkv.size(2);
   qkv_grad_finish_launch(bfp_mut(dqkv), bfp(dk_exp), bfp(dv_exp), cp, sp,
-                         groups, (int)(dqkv.size(1) * dqkv.size(2)),
-                         (int)dqkv.size(3) - 2, (int)dqkv.size(4),
-                         cur_stream());
+                         groups, per_table_row, (int)dqkv.size(3) - 2,
+                         (int)dqkv.size(4), cur_stream());
+}
+
+// ---- packed documents on the packed-QKV buffer ------------------------------
+// check_qkv plus the cu_seqlens checks of check_varlen.  As there, the table
+// is not read on the host: the caller validated its host copy, the segments
+// tile [0, b*s), so every q-slot row of dqkv (and every o / lse row) is
+// written exactly once and at::empty is correct.
+void check_qkv_varlen(const Tensor& qkv, const Tensor& cu, int64_t max_seqlen,
+                      const char* who) {
+  check_qkv(qkv, who);
+  const int64_t s = qkv.size(0), b = qkv.size(1);
+  const int64_t hq = qkv.size(2) * (qkv.size(3) - 2);
+  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() &&
+              cu.scalar_type() == at::kInt && cu.dim() == 1 &&
+              cu.numel() >= 2 && cu.device() == qkv.device(), who,
+              ": cu_seqlens must be a contiguous 1-D int32 tensor on qkv's "
+              "device with at least 2 entries");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= s, who,
+              ": need 1 <= max_seqlen <= s");
+  TORCH_CHECK(b * s < (1LL << 31), who, ": b*s must fit int32");
+  TORCH_CHECK((cu.numel() - 1) * hq <= 65535, who,
+              ": nseg*hq exceeds the grid limit (65535)");
+}
+
+// -> o [s, b, hq, d], lse [b, hq, s]
+std::tuple<Tensor, Tensor> flash_attn_qkv_varlen_fwd(
+    const Tensor& qkv, const Tensor& cu, int64_t max_seqlen, bool causal,
+    double scale) {
+  check_qkv_varlen(qkv, cu, max_seqlen, "flash_attn_qkv_varlen_fwd");
+  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
+  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
+  const int nseg = cu.numel() - 1;
+  auto o = at::empty({s, b, G * qpg, d}, qkv.options());
+  auto lse = at::empty({b, G * qpg, s}, qkv.options().dtype(at::kFloat));
+  flash_packed_varlen_fwd_launch(bfp(qkv), bfp_mut(o), lse.data_ptr<float>(),
+                                 cu.data_ptr<int>(), nseg, (int)max_seqlen,
+                                 b, s, G, qpg, d, (float)scale, causal,
+                                 cur_stream());
+  return {o, lse};
+}
+
+// -> dqkv (q slots = dq before the inverse rotation, k and v slots NOT yet
+// written), dk_exp, dv_exp [s, b, hq, d].  qkv_grad_finish_ completes dqkv.
+std::vector<Tensor> flash_attn_qkv_varlen_bwd(
+    const Tensor& dout, const Tensor& qkv, const Tensor& o, const Tensor& lse,
+    const Tensor& cu, int64_t max_seqlen, bool causal, double scale) {
+  check_qkv_varlen(qkv, cu, max_seqlen, "flash_attn_qkv_varlen_bwd");
+  CHECK_GPU(dout); CHECK_GPU(o); CHECK_GPU(lse);
+  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
+  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
+  const int hq = G * qpg;
+  const int nseg = cu.numel() - 1;
+  TORCH_CHECK(is_bf16(dout) && is_bf16(o) && o.dim() == 4 &&
+              o.size(0) == s && o.size(1) == b && o.size(2) == hq &&
+              o.size(3) == d && dout.sizes() == o.sizes(),
+              "flash_attn_qkv_varlen_bwd: dout/o must be bf16 [s, b, hq, d]");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 &&
+              lse.size(0) == b && lse.size(1) == hq && lse.size(2) == s,
+              "flash_attn_qkv_varlen_bwd: lse must be fp32 [b, hq, s]");
+  auto lsec = lse.contiguous();
+  auto di = at::empty({b, hq, s}, qkv.options().dtype(at::kFloat));
+  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, s, hq, d,
+                 cur_stream(), /*sbhd=*/true);
+  auto dqkv = at::empty_like(qkv);
+  auto dk_exp = at::empty({s, b, hq, d}, qkv.options());
+  auto dv_exp = at::empty({s, b, hq, d}, qkv.options());
+  flash_packed_varlen_bwd_launch(bfp(dout), bfp(qkv), lsec.data_ptr<float>(),
+                                 di.data_ptr<float>(), bfp_mut(dqkv),
+                                 bfp_mut(dk_exp), bfp_mut(dv_exp),
+                                 cu.data_ptr<int>(), nseg, (int)max_seqlen,
+                                 b, s, G, qpg, d, (float)scale, causal,
+                                 cur_stream());
+  return {dqkv, dk_exp, dv_exp};
 }
 
 // Single-token decode attention against a KV cache (serving path).
@@ -1066,6 +1150,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_qkv_", &rope_qkv_, py::arg("qkv"), py::arg("cos"), py::arg("sin"));
   m.def("flash_attn_qkv_fwd", &flash_attn_qkv_fwd, py::arg("qkv"), py::arg("causal"), py::arg("scale"));
   m.def("flash_attn_qkv_bwd", &flash_attn_qkv_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("scale"));
+  m.def("flash_attn_qkv_varlen_fwd", &flash_attn_qkv_varlen_fwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("scale"));
+  m.def("flash_attn_qkv_varlen_bwd", &flash_attn_qkv_varlen_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("scale"));
   m.def("qkv_grad_finish_", &qkv_grad_finish_, py::arg("dqkv"), py::arg("dk_exp"), py::arg("dv_exp"), py::arg("cos") = py::none(), py::arg("sin") = py::none());
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cur_len"), py::arg("scale"), py::arg("start") = 0);
   m.def("decode_attn_graph", &decode_attn_graph);

@@ -118,14 +118,16 @@ DEV_INLINE void rope_rotate8(const float* a, const float* b, const float* c,
 // In-place RoPE on the packed linear_qkv output x: [s, b, G, qpg+2, d]
 // (G kv groups; slots 0..qpg-1 of a group are its q heads, slot qpg is k,
 // slot qpg+1 is v).  Rotates the q and k slots and never touches v.
-// groups = s*b*G, bG = b*G.  Same arithmetic as rope_kernel (fp32, NEOX
-// halves, 16-byte packets, [s, d/2] tables), so the rotated q and k bits
-// equal those of the split-then-rotate path.  Each packet pair is read and
-// written by the same thread: safe in place.
+// groups = s*b*G.  tdiv is the number of consecutive groups that share one
+// table row: b*G for [s, d/2] tables, G for per-row [s, b, d/2] tables
+// (packed documents whose positions restart).  Same arithmetic as
+// rope_kernel (fp32, NEOX halves, 16-byte packets), so the rotated q and k
+// bits equal those of the split-then-rotate path.  Each packet pair is read
+// and written by the same thread: safe in place.
 __global__ void rope_qkv_kernel(__bf16* __restrict__ x,
                                 const float* __restrict__ cos_t,
                                 const float* __restrict__ sin_t,
-                                long groups, int bG, int qpg, int d) {
+                                long groups, int tdiv, int qpg, int d) {
   const int d2 = d / 2;
   const long packs_per_row = d2 / 8;
   const long per_group = (qpg + 1) * packs_per_row;
@@ -136,7 +138,7 @@ __global__ void rope_qkv_kernel(__bf16* __restrict__ x,
     const long r = idx - grp * per_group;
     const long slot = r / packs_per_row;
     const long j = (r - slot * packs_per_row) * 8;
-    const long s_idx = grp / bG;
+    const long s_idx = grp / tdiv;
     __bf16* x1 = x + (grp * (qpg + 2) + slot) * (long)d + j;
     __bf16* x2 = x1 + d2;
     float a[8], b[8], c[8], s[8], o1[8], o2[8];
@@ -166,7 +168,7 @@ __global__ void qkv_grad_finish_kernel(__bf16* __restrict__ dqkv,
                                        const __bf16* __restrict__ dv_exp,
                                        const float* __restrict__ cos_t,
                                        const float* __restrict__ sin_t,
-                                       long groups, int bG, int qpg, int d) {
+                                       long groups, int tdiv, int qpg, int d) {
   const int d2 = d / 2;
   const long packs_per_row = d2 / 8;
   const int first = ROPE ? 0 : qpg;
@@ -207,7 +209,7 @@ __global__ void qkv_grad_finish_kernel(__bf16* __restrict__ dqkv,
       }
     }
     if (ROPE && slot <= qpg) {
-      const long s_idx = grp / bG;
+      const long s_idx = grp / tdiv;
       float c[8], s[8], o1[8], o2[8];
       VecIO<float>::load(c, cos_t + s_idx * d2 + j);
       VecIO<float>::load(s, sin_t + s_idx * d2 + j);
@@ -224,29 +226,29 @@ __global__ void qkv_grad_finish_kernel(__bf16* __restrict__ dqkv,
 }  // namespace
 
 void rope_qkv_launch(__bf16* x, const float* cos_t, const float* sin_t,
-                     long groups, int bG, int qpg, int d, hipStream_t st) {
+                     long groups, int tdiv, int qpg, int d, hipStream_t st) {
   long total = groups * (qpg + 1) * (d / 2 / 8);
   int grid = galv_grid((total + 255) / 256);
   hipLaunchKernelGGL(rope_qkv_kernel, dim3(grid), dim3(256), 0, st, x, cos_t,
-                     sin_t, groups, bG, qpg, d);
+                     sin_t, groups, tdiv, qpg, d);
 }
 
 // cos_t == nullptr: no rotary embedding
 void qkv_grad_finish_launch(__bf16* dqkv, const __bf16* dk_exp,
                             const __bf16* dv_exp, const float* cos_t,
-                            const float* sin_t, long groups, int bG, int qpg,
+                            const float* sin_t, long groups, int tdiv, int qpg,
                             int d, hipStream_t st) {
   const bool rope = cos_t != nullptr;
   long total = groups * (rope ? qpg + 2 : 2) * (d / 2 / 8);
   int grid = galv_grid((total + 255) / 256);
   if (rope)
     hipLaunchKernelGGL((qkv_grad_finish_kernel<true>), dim3(grid), dim3(256),
-                       0, st, dqkv, dk_exp, dv_exp, cos_t, sin_t, groups, bG,
+                       0, st, dqkv, dk_exp, dv_exp, cos_t, sin_t, groups, tdiv,
                        qpg, d);
   else
     hipLaunchKernelGGL((qkv_grad_finish_kernel<false>), dim3(grid),
                        dim3(256), 0, st, dqkv, dk_exp, dv_exp, cos_t, sin_t,
-                       groups, bG, qpg, d);
+                       groups, tdiv, qpg, d);
 }
 
 template <typename T>

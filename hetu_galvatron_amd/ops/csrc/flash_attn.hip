@@ -1376,6 +1376,150 @@ void flash_packed_bwd_dkv_kernel(const __bf16* __restrict__ dout,
 #endif  // GALV_FLASH_PACKED_TU
 
 // ---------------------------------------------------------------------------
+// packed documents on the packed-QKV buffer: the varlen work mapping (one
+// workgroup per (segment, head, 256-row block) of a cu_seqlens table) with
+// the packed-QKV addressing.  For segment i, head h, t0 = cu[i], bi = t0/s,
+// p0 = t0 - bi*s, g = h/qpg, slot = h%qpg, hq = G*qpg:
+//   row stride (q, k, v, dq)   b*G*(qpg+2)*D
+//   q / dq base                (((p0*b + bi)*G + g)*(qpg+2) + slot)*D
+//   k, v                       pointers pre-offset by qpg*D, (qpg+1)*D; group
+//                              base ((p0*b + bi)*G + g)*(qpg+2)*D
+//   o, dout, dk_exp, dv_exp    [s, b, hq, D]: base ((p0*b + bi)*hq + h)*D,
+//                              row stride b*hq*D
+//   lse, di                    [b, hq, s]: base (bi*hq + h)*s + p0
+// sbhd only, sq = skv = len, off = 0, no bias, no window.  As in the varlen
+// module there is no complementary pairing, blocks past the end of a short
+// segment leave before touching memory, a malformed entry is an empty
+// segment, and each body has one call site and is inlined into it.
+// Compiled through flash_attn_qkv_varlen.hip, for the reason given above
+// for the varlen and packed modules.
+// ---------------------------------------------------------------------------
+#ifdef GALV_FLASH_PACKED_VARLEN_TU
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wignored-attributes"
+#define PACKED_VARLEN_INLINE_CALL [[clang::always_inline]]
+
+struct PackedSeg {
+  int len;  // tokens in the segment (0 = nothing to do)
+  long q_base, kv_base, o_base, lse_base;
+  int qkv_str, o_str;
+};
+
+template <int D>
+DEV_INLINE PackedSeg packed_seg(const int* __restrict__ cu, int b, int s,
+                                int G, int qpg) {
+  PackedSeg p;
+  const int hq = G * qpg;
+  const int seg = blockIdx.y / hq;
+  const int h = blockIdx.y - seg * hq;
+  const int g = h / qpg;
+  const int slot = h - g * qpg;
+  const int t0 = cu[seg];
+  const int len = cu[seg + 1] - t0;
+  const int bi = t0 / s;
+  const int p0 = t0 - bi * s;
+  // a malformed table (negative offset, past the last row, straddling a
+  // row) maps to "empty" so no address is ever formed from it
+  const bool ok = t0 >= 0 && len > 0 && bi < b && p0 + len <= s;
+  p.len = ok ? len : 0;
+  const long row = (long)p0 * b + bi;
+  const long grp = (row * G + g) * (qpg + 2);
+  p.q_base = (grp + slot) * D;
+  p.kv_base = grp * D;
+  p.o_base = (row * hq + h) * D;
+  p.lse_base = ((long)bi * hq + h) * s + p0;
+  p.qkv_str = b * G * (qpg + 2) * D;
+  p.o_str = b * hq * D;
+  return p;
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_packed_varlen_fwd_kernel(const __bf16* __restrict__ qkv,
+                                    __bf16* __restrict__ o,
+                                    float* __restrict__ lse,
+                                    const int* __restrict__ cu, int b, int s,
+                                    int G, int qpg, float scale,
+                                    bool causal) {
+  constexpr int KB = 64, QBF = 256;
+  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
+  // workgroup-uniform, before any barrier; also covers len == 0
+  if ((int)blockIdx.x * QBF >= p.len) return;
+  const __bf16* k = qkv + (long)qpg * D;
+  const __bf16* v = k + D;
+  const OutOwn oa{p.o_base, p.o_str};
+  const float sl2e = scale * 1.4426950408889634f;
+  PACKED_VARLEN_INLINE_CALL flash_fwd_block<D, false, false, OutOwn>(
+      blockIdx.x, qkv, k, v, o, lse, smem, p.q_base, p.kv_base, p.lse_base,
+      p.qkv_str, p.qkv_str, 0, p.len, p.len, sl2e, causal, nullptr, 0, 0,
+      oa);
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_packed_varlen_bwd_dq_kernel(const __bf16* __restrict__ dout,
+                                       const __bf16* __restrict__ qkv,
+                                       const float* __restrict__ lse,
+                                       const float* __restrict__ di,
+                                       __bf16* __restrict__ dqkv,
+                                       const int* __restrict__ cu, int b,
+                                       int s, int G, int qpg, float scale,
+                                       bool causal) {
+  constexpr int KB = 32, QBF = 256;
+  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
+  if ((int)blockIdx.x * QBF >= p.len) return;
+  const __bf16* k = qkv + (long)qpg * D;
+  const __bf16* v = k + D;
+  const OutOwn oa{p.o_base, p.o_str};
+  PACKED_VARLEN_INLINE_CALL flash_bwd_dq_block<D, false, false, OutOwn>(
+      blockIdx.x, dout, qkv, k, v, lse, di, dqkv, smem, p.q_base, p.kv_base,
+      p.lse_base, p.qkv_str, p.qkv_str, 0, p.len, p.len, scale, causal,
+      nullptr, 0, 0, oa);
+}
+
+template <int D>
+__global__ __launch_bounds__(512, 2)
+void flash_packed_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
+                                        const __bf16* __restrict__ qkv,
+                                        const float* __restrict__ lse,
+                                        const float* __restrict__ di,
+                                        __bf16* __restrict__ dk_exp,
+                                        __bf16* __restrict__ dv_exp,
+                                        const int* __restrict__ cu, int b,
+                                        int s, int G, int qpg, float scale,
+                                        bool causal) {
+  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
+  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  __shared__ __align__(16) float lsedi[4 * QT];
+  const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
+  if ((int)blockIdx.x * KBW >= p.len) return;
+  const __bf16* k = qkv + (long)qpg * D;
+  const __bf16* v = k + D;
+  const OutOwn oa{p.o_base, p.o_str};
+  // the two phases of flash_bwd_dkv_block, dV then dK; dk_exp / dv_exp
+  // carry hq heads in o's layout
+  PACKED_VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, false, false, false,
+                                                OutOwn>(
+      blockIdx.x, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
+      p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
+      p.o_str, 0, p.len, p.len, scale, causal, nullptr, nullptr, 0, 0, oa);
+  __syncthreads();
+  PACKED_VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, true, false, false,
+                                                OutOwn>(
+      blockIdx.x, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
+      p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
+      p.o_str, 0, p.len, p.len, scale, causal, nullptr, nullptr, 0, 0, oa);
+}
+
+#pragma clang diagnostic pop
+#endif  // GALV_FLASH_PACKED_VARLEN_TU
+
+// ---------------------------------------------------------------------------
 // MFMA layout probe: one-wave 32x32x16 GEMM from global memory laid out by
 // the assumed fragment maps. Validated against torch matmul on-device.
 // ---------------------------------------------------------------------------
@@ -1402,7 +1546,8 @@ __global__ void mfma_probe_kernel(const __bf16* __restrict__ A,  // [32][16]
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-#if !defined(GALV_FLASH_VARLEN_TU) && !defined(GALV_FLASH_PACKED_TU)
+#if !defined(GALV_FLASH_VARLEN_TU) && !defined(GALV_FLASH_PACKED_TU) && \
+    !defined(GALV_FLASH_PACKED_VARLEN_TU)
 template <int D>
 static void flash_fwd_launch_d(const __bf16* q, const __bf16* k,
                                const __bf16* v, __bf16* o, float* lse, int b,
@@ -1585,7 +1730,7 @@ void flash_varlen_bwd_launch(const __bf16* dout, const __bf16* q,
                                    hkv, scale, causal, sbhd, st);
 }
 
-#else  // GALV_FLASH_PACKED_TU
+#elif defined(GALV_FLASH_PACKED_TU)
 
 // packed QKV: the dense grids (and their underfill-aware pairing rule) with
 // hq = G*qpg heads
@@ -1643,6 +1788,66 @@ void flash_packed_bwd_launch(const __bf16* dout, const __bf16* qkv,
   else
     flash_packed_bwd_launch_d<128>(dout, qkv, lse, di, dqkv, dk_exp, dv_exp,
                                    b, s, G, qpg, scale, causal, st);
+}
+
+#else  // GALV_FLASH_PACKED_VARLEN_TU
+
+// packed QKV + varlen: the varlen grid with hq = G*qpg heads
+template <int D>
+static void flash_packed_varlen_fwd_launch_d(const __bf16* qkv, __bf16* o,
+                                             float* lse, const int* cu,
+                                             int nseg, int max_seqlen, int b,
+                                             int s, int G, int qpg,
+                                             float scale, bool causal,
+                                             hipStream_t st) {
+  dim3 grid((max_seqlen + 255) / 256, nseg * G * qpg);
+  hipLaunchKernelGGL((flash_packed_varlen_fwd_kernel<D>), grid, dim3(512), 0,
+                     st, qkv, o, lse, cu, b, s, G, qpg, scale, causal);
+}
+
+void flash_packed_varlen_fwd_launch(const __bf16* qkv, __bf16* o, float* lse,
+                                    const int* cu, int nseg, int max_seqlen,
+                                    int b, int s, int G, int qpg, int d,
+                                    float scale, bool causal,
+                                    hipStream_t st) {
+  if (d == 64)
+    flash_packed_varlen_fwd_launch_d<64>(qkv, o, lse, cu, nseg, max_seqlen,
+                                         b, s, G, qpg, scale, causal, st);
+  else
+    flash_packed_varlen_fwd_launch_d<128>(qkv, o, lse, cu, nseg, max_seqlen,
+                                          b, s, G, qpg, scale, causal, st);
+}
+
+template <int D>
+static void flash_packed_varlen_bwd_launch_d(
+    const __bf16* dout, const __bf16* qkv, const float* lse, const float* di,
+    __bf16* dqkv, __bf16* dk_exp, __bf16* dv_exp, const int* cu, int nseg,
+    int max_seqlen, int b, int s, int G, int qpg, float scale, bool causal,
+    hipStream_t st) {
+  dim3 grid((max_seqlen + 255) / 256, nseg * G * qpg);
+  hipLaunchKernelGGL((flash_packed_varlen_bwd_dq_kernel<D>), grid, dim3(512),
+                     0, st, dout, qkv, lse, di, dqkv, cu, b, s, G, qpg,
+                     scale, causal);
+  hipLaunchKernelGGL((flash_packed_varlen_bwd_dkv_kernel<D>), grid,
+                     dim3(512), 0, st, dout, qkv, lse, di, dk_exp, dv_exp,
+                     cu, b, s, G, qpg, scale, causal);
+}
+
+void flash_packed_varlen_bwd_launch(const __bf16* dout, const __bf16* qkv,
+                                    const float* lse, const float* di,
+                                    __bf16* dqkv, __bf16* dk_exp,
+                                    __bf16* dv_exp, const int* cu, int nseg,
+                                    int max_seqlen, int b, int s, int G,
+                                    int qpg, int d, float scale, bool causal,
+                                    hipStream_t st) {
+  if (d == 64)
+    flash_packed_varlen_bwd_launch_d<64>(dout, qkv, lse, di, dqkv, dk_exp,
+                                         dv_exp, cu, nseg, max_seqlen, b, s,
+                                         G, qpg, scale, causal, st);
+  else
+    flash_packed_varlen_bwd_launch_d<128>(dout, qkv, lse, di, dqkv, dk_exp,
+                                          dv_exp, cu, nseg, max_seqlen, b, s,
+                                          G, qpg, scale, causal, st);
 }
 
 #endif  // TU selection

@@ -380,6 +380,129 @@ def fused_qkv_attention(qkv, cos, sin, num_groups: int, q_per_group: int,
                            sbhd=True)
 
 
+class _FusedQKVAttentionVarlen(torch.autograd.Function):
+    """_FusedQKVAttention for packed documents: per-row RoPE tables
+    [s, b, d/2] (rank 3) as well as [s, d/2], and, with cu_seqlens, the
+    flash_packed_varlen_* kernels (ops/csrc/flash_attn.hip, packed varlen
+    section).  cu_seqlens None keeps the dense packed kernels and their
+    pairing.  Native only."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, geom, cu, max_seqlen, causal, scale):
+        ext = get_ext(False)
+        # see _FusedQKVAttention.forward
+        ctx.mark_dirty(qkv)
+        ctx.set_materialize_grads(False)
+        packed = qkv.view(*geom)
+        if cos is not None:
+            ext.rope_qkv_(packed, cos, sin)
+        if cu is None:
+            o, lse = ext.flash_attn_qkv_fwd(packed, causal, scale)
+        else:
+            o, lse = ext.flash_attn_qkv_varlen_fwd(packed, cu, max_seqlen,
+                                                   causal, scale)
+        ctx.save_for_backward(qkv, o, lse, cos, sin, cu)
+        ctx.geom = geom
+        ctx.max_seqlen = max_seqlen
+        ctx.causal = causal
+        ctx.scale = scale
+        return o, qkv
+
+    @staticmethod
+    def backward(ctx, do, _dbuf):
+        if do is None:
+            return (None,) * 8
+        qkv, o, lse, cos, sin, cu = ctx.saved_tensors
+        ext = get_ext(False)
+        if cu is None:
+            dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_bwd(
+                do.contiguous(), qkv.view(*ctx.geom), o, lse, ctx.causal,
+                ctx.scale)
+        else:
+            dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_varlen_bwd(
+                do.contiguous(), qkv.view(*ctx.geom), o, lse, cu,
+                ctx.max_seqlen, ctx.causal, ctx.scale)
+        ext.qkv_grad_finish_(dqkv, dk_exp, dv_exp, cos, sin)
+        return (dqkv.view(qkv.shape),) + (None,) * 7
+
+
+def _rope_qk_rows(q, k, cos, sin):
+    """apply_rope on q and k with [s, d/2] or per-row [s, b, d/2] tables.
+    Per-row: the batch folds into the row axis, [s*b, 1, h, d] with a
+    [s*b, d/2] table, as runtime.transformer.rope.apply_rope_qk does."""
+    if cos.dim() == 3:
+        s, b = q.shape[0], q.shape[1]
+        cos, sin = cos.reshape(s * b, -1), sin.reshape(s * b, -1)
+        qf = apply_rope(q.reshape(s * b, 1, *q.shape[2:]), cos, sin)
+        kf = apply_rope(k.reshape(s * b, 1, *k.shape[2:]), cos, sin)
+        return qf.view(q.shape), kf.view(k.shape)
+    return apply_rope(q, cos, sin), apply_rope(k, cos, sin)
+
+
+def fused_qkv_attention_varlen(qkv, cos, sin, num_groups: int,
+                               q_per_group: int, cu_seqlens=None,
+                               max_seqlen: Optional[int] = None,
+                               causal: bool = True,
+                               softmax_scale: Optional[float] = None):
+    """fused_qkv_attention for packed documents.
+
+    qkv as in fused_qkv_attention.  cos/sin: None, [s, d/2], or per-row
+    [s, b, d/2] (positions that restart per document; rank 3 selects it).
+    cu_seqlens/max_seqlen as in flash_attention_varlen: int32 [nseg+1]
+    offsets into the batch-major [b*s] stream that tile it without
+    straddling a row; a CPU table is validated and copied asynchronously, a
+    device table is trusted.  cu_seqlens=None attends over whole rows (the
+    reset_position_ids-only case).  Returns o [s, b, G*qpg, d].
+
+    The native path (bf16 on the GPU, head dim 64|128) CONSUMES qkv exactly
+    as fused_qkv_attention does.  Everything else runs the composition of
+    slice, apply_rope and flash_attention_varlen / flash_attention and
+    leaves qkv alone."""
+    s, b = qkv.shape[0], qkv.shape[1]
+    d = qkv.shape[2:].numel() // (num_groups * (q_per_group + 2))
+    geom = (s, b, num_groups, q_per_group + 2, d)
+    scale = softmax_scale if softmax_scale is not None \
+        else 1.0 / math.sqrt(d)
+    if cos is not None and cos.dim() not in (2, 3):
+        raise ValueError("fused_qkv_attention_varlen: cos/sin must be "
+                         "[s, d/2] or [s, b, d/2]")
+    if cu_seqlens is not None:
+        if max_seqlen is None:
+            raise ValueError("fused_qkv_attention_varlen: cu_seqlens needs "
+                             "max_seqlen")
+        max_seqlen = int(max_seqlen)
+        if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
+            raise ValueError("cu_seqlens must be a 1-D int32 tensor")
+        if not cu_seqlens.is_cuda:
+            ref.check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
+            if qkv.is_cuda:
+                cu_seqlens = cu_seqlens.to(qkv.device, non_blocking=True)
+        cu_seqlens = cu_seqlens.contiguous()
+    if use_native(qkv) and qkv.dtype == torch.bfloat16 and d in (64, 128):
+        if cos is not None:
+            cos = cos[:s].contiguous().float()
+            sin = sin[:s].contiguous().float()
+        # the buffer itself goes in, not a view of it (see
+        # fused_qkv_attention)
+        o, _ = _FusedQKVAttentionVarlen.apply(
+            qkv.contiguous(), cos, sin, geom, cu_seqlens, max_seqlen, causal,
+            scale)
+        return o
+    qkv = qkv.view(*geom)
+    q = qkv[:, :, :, :q_per_group].reshape(s, b, -1, d)
+    k = qkv[:, :, :, q_per_group].reshape(s, b, -1, d)
+    v = qkv[:, :, :, q_per_group + 1].reshape(s, b, -1, d)
+    q, k = q.contiguous(), k.contiguous()
+    if cos is not None:
+        q, k = _rope_qk_rows(q, k, cos, sin)
+    if cu_seqlens is None:
+        return flash_attention(q, k, v.contiguous(), causal=causal,
+                               softmax_scale=softmax_scale, sbhd=True)
+    return flash_attention_varlen(q, k, v.contiguous(), cu_seqlens,
+                                  max_seqlen, causal=causal,
+                                  softmax_scale=softmax_scale, sbhd=True)
+
+
 class _FlashBiasAttention(torch.autograd.Function):
     """Biased flash attention (t5 relative bias [hq, sq, skv]) with grads
     for q/k/v AND the bias (dbias batch-summed, flows back into the bias

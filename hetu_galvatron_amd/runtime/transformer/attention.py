@@ -29,7 +29,7 @@ from .attention_impl import (
     flash_bias_attention, local_attention,
 )
 from .rope import apply_rope_qk
-from ...ops import fused_qkv_attention
+from ...ops import fused_qkv_attention, fused_qkv_attention_varlen
 
 
 def _dropout_attention(q, k, v, causal, scale, p):
@@ -146,18 +146,29 @@ class SelfAttention(nn.Module):
         over the global kv axis."""
         qkv = self.linear_qkv(x)  # [s, b, (hq_l + 2*hkv_l)*d]
         s, b = qkv.shape[0], qkv.shape[1]
-        if self.fused_qkv and self.core_attention is None \
-                and attn_bias is None and cu_seqlens is None \
-                and self.q_layernorm is None \
-                and not (self.attn_dropout > 0 and self.training) \
-                and not self.rope_interleaved \
-                and (cos is None or cos.dim() == 2):
+        fusable = self.fused_qkv and self.core_attention is None \
+            and attn_bias is None and self.q_layernorm is None \
+            and not (self.attn_dropout > 0 and self.training) \
+            and not self.rope_interleaved
+        packed_docs = cu_seqlens is not None \
+            or (cos is not None and cos.dim() == 3)
+        if fusable and not packed_docs:
             # plain local path: RoPE and flash attention run on the packed
             # buffer (consumed: linear_qkv keeps no reference to its output)
             o = fused_qkv_attention(
                 qkv, cos, sin, self.num_groups_local, self.q_per_group,
                 causal=self.causal, softmax_scale=self.softmax_scale,
                 window=self.window)
+            return self.linear_proj(o.reshape(s, b, -1))
+        if fusable and self.window is None \
+                and (cu_seqlens is None or self.attn_dropout == 0):
+            # packed documents (segments and/or per-row RoPE tables) on the
+            # packed buffer; a window or inactive dropout with cu_seqlens
+            # goes on to the refusal below
+            o = fused_qkv_attention_varlen(
+                qkv, cos, sin, self.num_groups_local, self.q_per_group,
+                cu_seqlens=cu_seqlens, max_seqlen=max_seqlen,
+                causal=self.causal, softmax_scale=self.softmax_scale)
             return self.linear_proj(o.reshape(s, b, -1))
         qkv = qkv.view(s, b, self.num_groups_local, self.q_per_group + 2,
                        self.head_dim)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|qkv|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -161,6 +161,79 @@ def bench_qkv(iters, repeats=9):
               f"[{lo*1e3:.3f}, {hi*1e3:.3f}]")
 
 
+def bench_qkv_varlen(iters, repeats=9, composition_only=False):
+    """bench_qkv for packed documents: linear_qkv output -> attention output
+    with cu_seqlens and per-row [s, b, d/2] RoPE tables, b4 s4096 G8 qpg4
+    d128 causal bf16, every row of the batch segmented the same way:
+      1x4096   one document per row (the unpaired varlen cost on both sides)
+      16x256   sixteen documents per row
+      mixed    2048 + 1024 + 512 + 256 + 255 + 1
+      composition   slice q/k/v, apply_rope_qk per-row,
+                    flash_attention_varlen(sbhd) and autograd's backward
+      fused         ops.fused_qkv_attention_varlen
+    Both rows start from a fresh x.clone(), as in bench_qkv.
+    composition_only skips the fused row (to time another build of the
+    extension that predates the op with the same code)."""
+    from hetu_galvatron_amd.ops import flash_attention_varlen
+    from hetu_galvatron_amd.ops.reference_ops import rope_freqs
+    from hetu_galvatron_amd.runtime.transformer.rope import apply_rope_qk
+    s, b, G, qpg, d = 4096, 4, 8, 4, 128
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randn(s, b, G, qpg + 2, d, device="cuda",
+                    generator=g).bfloat16().requires_grad_(True)
+    do = torch.randn(s, b, G * qpg, d, device="cuda", generator=g).bfloat16()
+    cos_t, sin_t = rope_freqs(s, d, device="cuda")
+
+    def fwd_bwd(fn):
+        def run():
+            x.grad = None
+            fn().backward(do)
+        return run
+
+    for label, lens in (("1x4096", [4096]), ("16x256", [256] * 16),
+                        ("mixed", [2048, 1024, 512, 256, 255, 1])):
+        assert sum(lens) == s
+        offs = [0]
+        for _ in range(b):
+            for n in lens:
+                offs.append(offs[-1] + n)
+        cu = torch.tensor(offs, dtype=torch.int32, device="cuda")
+        maxlen = max(lens)
+        pos = torch.cat([torch.arange(n) for n in lens]).cuda()
+        cos = cos_t[pos][:, None].expand(s, b, d // 2).contiguous()
+        sin = sin_t[pos][:, None].expand(s, b, d // 2).contiguous()
+
+        def composition():
+            xc = x.clone()
+            q = xc[:, :, :, :qpg].reshape(s, b, -1, d)
+            k = xc[:, :, :, qpg].reshape(s, b, -1, d)
+            v = xc[:, :, :, qpg + 1].reshape(s, b, -1, d)
+            q, k = apply_rope_qk(q.contiguous(), k.contiguous(), cos, sin)
+            return flash_attention_varlen(q, k, v.contiguous(), cu, maxlen,
+                                          causal=True, sbhd=True)
+
+        def fused():
+            from hetu_galvatron_amd.ops import fused_qkv_attention_varlen
+            return fused_qkv_attention_varlen(
+                x.clone(), cos, sin, G, qpg, cu_seqlens=cu,
+                max_seqlen=maxlen, causal=True)
+
+        rows = [("composition", composition)]
+        if not composition_only:
+            rows.append(("fused", fused))
+            with torch.no_grad():
+                assert torch.equal(fused(), composition()), \
+                    "the fused op must reproduce the composition"
+        for name, fn in rows:
+            with torch.no_grad():
+                tf, lo, hi = median_of_windows(fn, iters, repeats)
+            print(f"qkv-varlen {label:7s} {name:12s} fwd     {tf*1e3:7.3f} ms"
+                  f" [{lo*1e3:.3f}, {hi*1e3:.3f}]")
+            tb, lo, hi = median_of_windows(fwd_bwd(fn), iters, repeats)
+            print(f"qkv-varlen {label:7s} {name:12s} fwd+bwd {tb*1e3:7.3f} ms"
+                  f" [{lo*1e3:.3f}, {hi*1e3:.3f}]")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -246,6 +319,8 @@ def main():
                     help="timed windows per row (varlen and qkv entries)")
     ap.add_argument("--dense-only", action="store_true",
                     help="varlen entry: time only the dense kernels")
+    ap.add_argument("--composition-only", action="store_true",
+                    help="qkv-varlen entry: time only the composition")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     fns = {"flash": bench_flash, "norms": bench_norms,
@@ -253,7 +328,9 @@ def main():
            "bias": bench_bias,
            "varlen": lambda it: bench_varlen(it, args.repeats,
                                              args.dense_only),
-           "qkv": lambda it: bench_qkv(it, args.repeats)}
+           "qkv": lambda it: bench_qkv(it, args.repeats),
+           "qkv-varlen": lambda it: bench_qkv_varlen(
+               it, args.repeats, args.composition_only)}
     if args.what == "all":
         for f in fns.values():
             f(args.iters)
