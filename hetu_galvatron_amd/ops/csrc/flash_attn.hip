@@ -15,14 +15,16 @@
 //   P redistributed to PV fragments by cvt_pk_bf16 + permlane32_swap
 //   (no LDS round-trip); PV computed as O^T = mfma(V^T, P^T) so the
 //   running rescale is a plain per-lane multiply;
-//   V staged TRANSPOSED straight from global (coalesced 2-byte column
-//   loads -> b128 LDS writes; the v1 scalar ds_write_b16 transpose was
-//   14-37% of wave cycles in SQ_LDS_BANK_CONFLICT);
+//   V staged by rows like K (16-byte loads -> b128 LDS writes) into a
+//   swizzled image and read transposed with ds_read_b64_tr_b16 (the v1
+//   scalar ds_write_b16 transpose was 14-37% of wave cycles in
+//   SQ_LDS_BANK_CONFLICT; v2 staged a second, transposed image from
+//   strided 2-byte global loads);
 //   async-stage split (T14): next tile's global loads issue before the
 //   current tile's compute, LDS writes land after the barrier;
 //   per-wave causal tile skip.
-// Backward keeps the v1 two-kernel (dq + expanded dkv) structure with the
-// same column-load transpose staging.
+// Backward keeps the v1 two-kernel (dq + expanded dkv) structure; K (dq)
+// and Q / dO (dkv) are held once and read both by rows and transposed.
 #include "common.h"
 
 namespace {
@@ -38,24 +40,160 @@ DEV_INLINE unsigned pack_bf16(float lo, float hi) {
   return cv.u;
 }
 
-typedef __attribute__((ext_vector_type(8))) unsigned short ushort8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 // 16 bias values for one 32-key D-layout column: row(r) = 8*(r>>2) +
 // 4*hi + (r&3) — each r-quad is 4 contiguous bf16, so 4 8-byte loads
 // cover the column.  base must be 4-element aligned (callers pass
-// kv0 + 4*hi with kv0 % 32 == 0); the clamp keeps the tail in bounds
-// (masked lanes discard the values).
+// kv0 + 4*hi with kv0 % 32 == 0).  A quad that reaches past the row end is
+// loaded from the row's last 4 elements and shifted down, so that the keys
+// of a row whose length is no multiple of 4 still get their own bias
+// (clamping the quad to a 4-aligned start gave the last limit % 4 keys the
+// bias of earlier ones); what is shifted in belongs to masked keys.
 DEV_INLINE void load_bias16(const __bf16* brow, int base, int limit,
                             float* out /*16*/) {
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
-    int idx = base + 8 * g;
-    idx = min(idx, max((limit - 4) & ~3, 0));
-    const bf16x4 b4 = *reinterpret_cast<const bf16x4*>(brow + idx);
+    const int idx = base + 8 * g;
+    const int cl = min(idx, max(limit - 4, 0));
+    union { bf16x4 v; unsigned long long u; } b4;
+    b4.v = *reinterpret_cast<const bf16x4*>(brow + cl);
+    b4.u >>= 16 * min(idx - cl, 3);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) out[4 * g + j] = (float)b4[j];
+    for (int j = 0; j < 4; ++j) out[4 * g + j] = (float)b4.v[j];
   }
+}
+
+// ---------------------------------------------------------------------------
+// One LDS image per staged [rows][D] tile, read both by rows (ds_read_b128,
+// the first product of every body) and by columns (ds_read_b64_tr_b16, the
+// second product), so no tile is fetched or held twice.
+//
+// tile_off(row, ch) is the element offset of 16-byte chunk ch (0..D/8-1) of
+// row `row`: 8-row x 32-column subtiles of 512 B, the four chunks of a
+// subtile row XORed with bits 2..3 of the row.  The image is dense
+// (rows*D elements, no padding).  By the bank rule (bank = (byte/4) % 64
+// for b128 / b64 / tr reads, % 32 for writes):
+//   row read   lane l reads row l & 31 (+ const), all lanes of a half one
+//              ch.  ds_read_b128 is served in groups of 16 lanes made of
+//              four aligned 4-lane runs (lanes 0-3, 12-15, 20-27 and so
+//              on), i.e. rows 4n..4n+3 for four different n, each n with
+//              its own n & 3: row & 3 picks the 64-byte quarter, the XOR
+//              key n & 3 the slot in it -> 16 distinct slots, conflict-free;
+//   tr read    a 32-lane half holds rows r0..r0+3 (r0 % 4 == 0) x the four
+//              chunks of one subtile = 256 contiguous bytes, conflict-free;
+//   write      8 consecutive lanes hold two rows x four chunks of a subtile
+//              (stage_map) = 128 contiguous bytes, conflict-free.
+// Reads that differ by ks / dt / +32 rows differ by constants (or by the
+// ks&1 bit inside the XOR), so each kind needs two address registers.
+// ---------------------------------------------------------------------------
+#define TILE_FN __host__ __device__ __forceinline__ constexpr
+template <int D>
+TILE_FN int tile_off(int row, int ch) {
+  return 8 * D * (row >> 3) + 256 * (ch >> 2) + 32 * (row & 7) +
+         8 * ((ch & 3) ^ ((row >> 2) & 3));
+}
+
+// staging pack p of thread tid -> (row, chunk): 4 lanes cover 64 B of a
+// row, the next 4 the row below, then the next subtile of the row pair; a
+// wave covers whole rows (D=128: 4, D=64: 8), so the 16-byte global loads
+// stay coalesced.  A thread's packs are 4096/D rows apart in one chunk, so
+// they share their addresses up to a constant.
+template <int D>
+DEV_INLINE void stage_map(int tid, int p, int& row, int& ch) {
+  const int rest = tid >> 3;
+  row = 2 * (rest / (D / 32)) + ((tid >> 2) & 1) + p * (4096 / D);
+  ch = 4 * (rest % (D / 32)) + (tid & 3);
+}
+
+// Offset of a row read, tile_off(rb + col, 2*ks + hi) for lane l (col =
+// l & 31, hi = l >> 5) and rb % 16 == 0, with the constants split off: one
+// lane term, XOR 16 for odd ks.  tile_reads_match_tile_off ties it to
+// tile_off at compile time.
+template <int D>
+TILE_FN int tile_row_off(int lane, int rb, int ks) {
+  const int col = lane & 31, hi = lane >> 5;
+  const int lane_off = 8 * D * (col >> 3) + 32 * (col & 7) +
+                       8 * (hi ^ ((col >> 2) & 3));
+  return (lane_off ^ (16 * (ks & 1))) + D * rb + 256 * (ks >> 1);
+}
+
+// A/B fragment of a row read: T[rb + col][16*ks + 8*hi + j], j = 0..7
+template <int D>
+DEV_INLINE bf16x8 tile_row_frag(const __bf16* t, int rb, int ks, int lane) {
+  return *reinterpret_cast<const bf16x8*>(t + tile_row_off<D>(lane, rb, ks));
+}
+
+// A fragment of the transposed product: lane l (col = l & 31, hi = l >> 5)
+// gets T[row0 + 8*hi + j][32*dt + col], j = 0..7 — what one b128 read of a
+// transposed image would give.  ds_read_b64_tr_b16 serves 16-lane groups:
+// lane 4q+p of a group supplies the address of row q, columns 4p..4p+3 of a
+// 4 x 16 block and lane i receives column i.  Group g = l >> 4 has hi = g>>1
+// and columns 32*dt + 16*(g&1) + (0..15), i.e. chunk 4*dt + 2*(g&1) +
+// (p>>1), half p & 1; the first read takes rows row0 + 8*hi + q (j = 0..3),
+// the second the rows 4 below (j = 4..7).  With row0 % 16 == 0 the XOR key
+// (row >> 2) & 3 is 2*hi for the first read and 2*hi + 1 for the second, so
+// tile_off reduces to one lane term; the second read is 4 rows (128
+// elements) on with the chunk's low bit flipped (XOR 8).
+// Every lane's address is 8-byte aligned and inside the tile.  EXEC must be
+// all ones: call only under wave-uniform control flow.
+template <int D>
+TILE_FN int tile_tr_off(int lane, int row0, int dt, int second) {
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int hi = g >> 1;
+  const int lane_off = 8 * D * hi + 32 * q + 16 * ((g & 1) ^ hi) + 4 * p;
+  return D * row0 + 256 * dt + (second ? (lane_off ^ 8) + 128 : lane_off);
+}
+
+typedef __attribute__((ext_vector_type(4))) short tr_short4;
+template <int D>
+DEV_INLINE bf16x8 tile_tr_frag(const __bf16* t, int row0, int dt, int lane) {
+  typedef __attribute__((address_space(3))) tr_short4 lds_short4;
+  union { tr_short4 h[2]; bf16x8 f; } u;
+  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_short4*)(t + tile_tr_off<D>(lane, row0, dt, 0)));
+  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_short4*)(t + tile_tr_off<D>(lane, row0, dt, 1)));
+  return u.f;
+}
+
+// The reduced read offsets against tile_off, for every lane, 16-row step,
+// ks and dt of a 64-row tile (the largest staged): the row read is chunk
+// 2*ks + hi of row rb + col; lane 4q+p of group g of the transposed read
+// is half p & 1 of chunk 4*dt + 2*(g&1) + (p>>1) of row row0 + 8*(g>>1) + q
+// (+ 4 for the second read), 8-byte aligned.
+template <int D>
+constexpr bool tile_reads_match_tile_off() {
+  for (int lane = 0; lane < 64; ++lane)
+    for (int r16 = 0; r16 < 64; r16 += 16) {
+      const int col = lane & 31, hi = lane >> 5;
+      for (int ks = 0; ks < D / 16; ++ks)
+        if (tile_row_off<D>(lane, r16, ks) !=
+            tile_off<D>(r16 + col, 2 * ks + hi))
+          return false;
+      const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+      for (int dt = 0; dt < D / 32; ++dt)
+        for (int second = 0; second < 2; ++second) {
+          const int off = tile_tr_off<D>(lane, r16, dt, second);
+          const int row = r16 + 8 * (g >> 1) + q + 4 * second;
+          const int ch = 4 * dt + 2 * (g & 1) + (p >> 1);
+          if (off != tile_off<D>(row, ch) + 4 * (p & 1) || off % 4 != 0)
+            return false;
+        }
+    }
+  return true;
+}
+static_assert(tile_reads_match_tile_off<64>() &&
+                  tile_reads_match_tile_off<128>(),
+              "tile_row_off / tile_tr_off diverge from tile_off");
+
+// four D-layout registers r = 4g..4g+3 are 4 contiguous columns of the
+// lane's output row (mfma32_d_row): one 8-byte store
+DEV_INLINE void store_d_quad(__bf16* row, int dt, int g, int hi, float a,
+                             float b, float c, float d) {
+  bf16x4 pk;
+  pk[0] = (__bf16)a; pk[1] = (__bf16)b; pk[2] = (__bf16)c; pk[3] = (__bf16)d;
+  *reinterpret_cast<bf16x4*>(row + dt * 32 + 8 * g + 4 * hi) = pk;
 }
 
 // Where the o / dout rows of a head live.  The dense and varlen kernels keep
@@ -91,13 +229,11 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
                      long bias_base = 0, int window = 0, OA oa = OA()) {
   constexpr int KB = 64;            // kv tile
   constexpr int QBF = 256;          // q rows per workgroup (8 waves x 32)
-  constexpr int KROW = D + 8;       // padded K row (bf16 elems)
-  constexpr int VTROW = KB + 8;     // padded transposed-V row
   constexpr int NK = D / 16;        // S^T K-slices
   constexpr int ND = D / 32;        // 32-wide d tiles of O^T
   constexpr int KPT = D / 64;       // staging packs per thread (512 thr)
 
-  constexpr int BUFSZ = KB * KROW + D * VTROW;
+  constexpr int BUFSZ = 2 * KB * D;  // K rows + V rows (tile_off images)
   __bf16* smem = smem_base;
 
   const int tid = threadIdx.x;
@@ -134,8 +270,7 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
   }
 
   // staged registers for the next tile
-  bf16x8 kst[KPT];
-  ushort8 vst[KPT];
+  bf16x8 kst[KPT], vst[KPT];
 
   // Guards are hoisted out of the load loops: per-element branches around
   // staged loads make hipcc wait vmcnt(0) after EACH load (32 serialized
@@ -146,57 +281,31 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
     const bool full = (kv0 + KB <= skv);
 #pragma unroll
     for (int p = 0; p < KPT; ++p) {
-      const int idx = tid + p * 512;
-      const int row = idx / (D / 8);
-      const int c8 = (idx - row * (D / 8)) * 8;
+      int row, ch;
+      stage_map<D>(tid, p, row, ch);
       const int kg = kv0 + row;
       if (full) {
-        kst[p] = *reinterpret_cast<const bf16x8*>(
-            k + kv_base + (long)kg * kv_stride + c8);
+        const long g = kv_base + (long)kg * kv_stride + ch * 8;
+        kst[p] = *reinterpret_cast<const bf16x8*>(k + g);
+        vst[p] = *reinterpret_cast<const bf16x8*>(v + g);
       } else {
-        bf16x8 t = *reinterpret_cast<const bf16x8*>(
-            k + kv_base + (long)min(kg, skv - 1) * kv_stride + c8);
-        kst[p] = kg < skv ? t : (bf16x8)(__bf16(0.f));
+        const long g = kv_base + (long)min(kg, skv - 1) * kv_stride + ch * 8;
+        bf16x8 tk = *reinterpret_cast<const bf16x8*>(k + g);
+        bf16x8 tv = *reinterpret_cast<const bf16x8*>(v + g);
+        kst[p] = kg < skv ? tk : (bf16x8)(__bf16(0.f));
+        vst[p] = kg < skv ? tv : (bf16x8)(__bf16(0.f));
       }
-    }
-#pragma unroll
-    for (int p = 0; p < KPT; ++p) {
-      const int idx = tid + p * 512;
-      const int c = idx & (D - 1);
-      const int kc = (idx / D) * 8;
-      const unsigned short* vb = reinterpret_cast<const unsigned short*>(
-          v + kv_base) + c;
-      ushort8 vv;
-      if (full) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          vv[j] = vb[(long)(kv0 + kc + j) * kv_stride];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          unsigned short t = vb[(long)min(kv0 + kc + j, skv - 1) * kv_stride];
-          vv[j] = kv0 + kc + j < skv ? t : (unsigned short)0;
-        }
-      }
-      vst[p] = vv;
     }
   };
   auto stage_write = [&](int buf) {
     __bf16* k_lds = smem + buf * BUFSZ;
-    __bf16* vt_lds = k_lds + KB * KROW;
+    __bf16* v_lds = k_lds + KB * D;
 #pragma unroll
     for (int p = 0; p < KPT; ++p) {
-      const int idx = tid + p * 512;
-      const int row = idx / (D / 8);
-      const int c8 = (idx - row * (D / 8)) * 8;
-      *reinterpret_cast<bf16x8*>(k_lds + row * KROW + c8) = kst[p];
-    }
-#pragma unroll
-    for (int p = 0; p < KPT; ++p) {
-      const int idx = tid + p * 512;
-      const int c = idx & (D - 1);
-      const int kc = (idx / D) * 8;
-      *reinterpret_cast<ushort8*>(vt_lds + c * VTROW + kc) = vst[p];
+      int row, ch;
+      stage_map<D>(tid, p, row, ch);
+      *reinterpret_cast<bf16x8*>(k_lds + tile_off<D>(row, ch)) = kst[p];
+      *reinterpret_cast<bf16x8*>(v_lds + tile_off<D>(row, ch)) = vst[p];
     }
   };
 
@@ -208,7 +317,7 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
   for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KB) {
     const bool have_next = kv0 + KB < kv_end;
     const __bf16* k_lds = smem + cur * BUFSZ;
-    const __bf16* vt_lds = k_lds + KB * KROW;
+    const __bf16* v_lds = k_lds + KB * D;
     if (have_next) stage_load(kv0 + KB);  // async: lands at stage_write
 
     if (kv0 < kv_last_w && kv0 + KB > kv_first_w) {  // per-wave skips
@@ -216,10 +325,8 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
       f32x16 st0 = (f32x16)(0.f), st1 = (f32x16)(0.f);
 #pragma unroll
       for (int ks = 0; ks < NK; ++ks) {
-        bf16x8 k0 = *reinterpret_cast<const bf16x8*>(
-            k_lds + col * KROW + ks * 16 + 8 * hi);
-        bf16x8 k1 = *reinterpret_cast<const bf16x8*>(
-            k_lds + (col + 32) * KROW + ks * 16 + 8 * hi);
+        bf16x8 k0 = tile_row_frag<D>(k_lds, 0, ks, lane);
+        bf16x8 k1 = tile_row_frag<D>(k_lds, 32, ks, lane);
         st0 = mfma32_bf16(k0, qf[ks], st0);
         st1 = mfma32_bf16(k1, qf[ks], st1);
       }
@@ -316,8 +423,7 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
         for (int g = 0; g < 4; ++g) pb.u[g] = w[ks * 4 + g];
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) {
-          bf16x8 va = *reinterpret_cast<const bf16x8*>(
-              vt_lds + (col + 32 * dt) * VTROW + ks * 16 + 8 * hi);
+          bf16x8 va = tile_tr_frag<D>(v_lds, ks * 16, dt, lane);
           ot[dt] = mfma32_bf16(va, pb.f, ot[dt]);
         }
       }
@@ -359,7 +465,7 @@ void flash_fwd_kernel(const __bf16* __restrict__ q,
                       bool paired = true, bool sbhd = false,
                       int window = 0) {
   constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const int bh = blockIdx.y;
   const int bi = bh / hq;
@@ -456,13 +562,11 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
                         long bias_base = 0, int window = 0, OA oa = OA()) {
   constexpr int KB = 32;         // kv tile
   constexpr int QBF = 256;       // q rows per workgroup (8 waves x 32)
-  constexpr int KROW = D + 8;
-  constexpr int KTROW = KB + 8;
   constexpr int NK = D / 16;
   constexpr int ND = D / 32;
   constexpr int KPT = (KB * D / 8 + 511) / 512;  // row packs per thread
 
-  constexpr int BUFSZ = 2 * KB * KROW + D * KTROW;
+  constexpr int BUFSZ = 2 * KB * D;  // K rows + V rows (tile_off images)
   __bf16* smem = smem_base;
 
   const int tid = threadIdx.x;
@@ -504,7 +608,6 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
   }
 
   bf16x8 kst[KPT], vst_r[KPT];
-  ushort8 ktst[KPT * 2];
 
   auto stage_load = [&](int kv0) {
     const bool full = (kv0 + KB <= skv);
@@ -512,61 +615,30 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
     for (int p = 0; p < KPT; ++p) {
       const int idx = tid + p * 512;
       if (idx >= KB * D / 8) break;
-      const int row = idx / (D / 8);
-      const int c8 = (idx - row * (D / 8)) * 8;
+      int row, ch;
+      stage_map<D>(tid, p, row, ch);
       const int kg = full ? kv0 + row : min(kv0 + row, skv - 1);
       kst[p] = *reinterpret_cast<const bf16x8*>(
-          k + kv_base + (long)kg * kv_stride + c8);
+          k + kv_base + (long)kg * kv_stride + ch * 8);
       vst_r[p] = *reinterpret_cast<const bf16x8*>(
-          v + kv_base + (long)kg * kv_stride + c8);
+          v + kv_base + (long)kg * kv_stride + ch * 8);
       if (!full && kv0 + row >= skv) {
         kst[p] = (bf16x8)(__bf16(0.f));
         vst_r[p] = (bf16x8)(__bf16(0.f));
       }
     }
-#pragma unroll
-    for (int p = 0; p < KPT * 2; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= D * KB / 8) break;
-      const int c = idx & (D - 1);
-      const int kc = (idx / D) * 8;
-      const unsigned short* kb = reinterpret_cast<const unsigned short*>(
-          k + kv_base) + c;
-      ushort8 t;
-      if (full) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          t[j] = kb[(long)(kv0 + kc + j) * kv_stride];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          unsigned short x = kb[(long)min(kv0 + kc + j, skv - 1) * kv_stride];
-          t[j] = kv0 + kc + j < skv ? x : (unsigned short)0;
-        }
-      }
-      ktst[p] = t;
-    }
   };
   auto stage_write = [&](int buf) {
     __bf16* k_lds = smem + buf * BUFSZ;
-    __bf16* v_lds = k_lds + KB * KROW;
-    __bf16* kt_lds = v_lds + KB * KROW;
+    __bf16* v_lds = k_lds + KB * D;
 #pragma unroll
     for (int p = 0; p < KPT; ++p) {
       const int idx = tid + p * 512;
       if (idx >= KB * D / 8) break;
-      const int row = idx / (D / 8);
-      const int c8 = (idx - row * (D / 8)) * 8;
-      *reinterpret_cast<bf16x8*>(k_lds + row * KROW + c8) = kst[p];
-      *reinterpret_cast<bf16x8*>(v_lds + row * KROW + c8) = vst_r[p];
-    }
-#pragma unroll
-    for (int p = 0; p < KPT * 2; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= D * KB / 8) break;
-      const int c = idx & (D - 1);
-      const int kc = (idx / D) * 8;
-      *reinterpret_cast<ushort8*>(kt_lds + c * KTROW + kc) = ktst[p];
+      int row, ch;
+      stage_map<D>(tid, p, row, ch);
+      *reinterpret_cast<bf16x8*>(k_lds + tile_off<D>(row, ch)) = kst[p];
+      *reinterpret_cast<bf16x8*>(v_lds + tile_off<D>(row, ch)) = vst_r[p];
     }
   };
 
@@ -580,8 +652,7 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
   for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KB) {
     const bool have_next = kv0 + KB < kv_end;
     const __bf16* k_lds = smem + cur * BUFSZ;
-    const __bf16* v_lds = k_lds + KB * KROW;
-    const __bf16* kt_lds = v_lds + KB * KROW;
+    const __bf16* v_lds = k_lds + KB * D;
     if (have_next) stage_load(kv0 + KB);
 
     if (kv0 < kv_last_w && kv0 + KB > kv_first_w) {
@@ -589,11 +660,9 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
       f32x16 st = (f32x16)(0.f), dp = (f32x16)(0.f);
 #pragma unroll
       for (int ks = 0; ks < NK; ++ks) {
-        bf16x8 kb = *reinterpret_cast<const bf16x8*>(
-            k_lds + col * KROW + ks * 16 + 8 * hi);
+        bf16x8 kb = tile_row_frag<D>(k_lds, 0, ks, lane);
         st = mfma32_bf16(kb, qf[ks], st);
-        bf16x8 vb = *reinterpret_cast<const bf16x8*>(
-            v_lds + col * KROW + ks * 16 + 8 * hi);
+        bf16x8 vb = tile_row_frag<D>(v_lds, 0, ks, lane);
         dp = mfma32_bf16(vb, dof[ks], dp);
       }
 
@@ -647,8 +716,7 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
         for (int g = 0; g < 4; ++g) db.u[g] = w[kh * 4 + g];
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) {
-          bf16x8 ka = *reinterpret_cast<const bf16x8*>(
-              kt_lds + (col + 32 * dt) * KTROW + kh * 16 + 8 * hi);
+          bf16x8 ka = tile_tr_frag<D>(k_lds, kh * 16, dt, lane);
           dq_acc[dt] = mfma32_bf16(ka, db.f, dq_acc[dt]);
         }
       }
@@ -666,8 +734,9 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        dqr[dt * 32 + mfma32_d_row(lane, r)] = (__bf16)dq_acc[dt][r];
+      for (int g = 0; g < 4; ++g)
+        store_d_quad(dqr, dt, g, hi, dq_acc[dt][4 * g], dq_acc[dt][4 * g + 1],
+                     dq_acc[dt][4 * g + 2], dq_acc[dt][4 * g + 3]);
   }
 }
 
@@ -686,7 +755,7 @@ void flash_bwd_dq_kernel(const __bf16* __restrict__ dout,
                          bool paired = true, bool sbhd = false,
                          int window = 0) {
   constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const int bh = blockIdx.y;
   const int bi = bh / hq;
@@ -754,14 +823,12 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
                          long bias_base = 0, int window = 0, OA oa = OA()) {
   constexpr int QT = 64;           // q tile (2 mfma halves per stage)
   constexpr int KBW = 256;         // keys per workgroup (8 waves x 32)
-  constexpr int QROW = D + 8;
-  constexpr int TROW = QT + 8;
   constexpr int NK = D / 16;
   constexpr int ND = D / 32;
   constexpr int QPT = (QT * D / 8 + 511) / 512;   // row packs per thread
 
-  // LDS per buffer: q rows + transposed image (+ dO rows in the dK phase)
-  constexpr int BUFSZ = (DKPH ? 2 : 1) * QT * QROW + D * TROW;
+  // LDS per buffer: q rows + dO rows (tile_off images), in both phases
+  constexpr int BUFSZ = 2 * QT * D;
   __bf16* smem = smem_base;
   float (*lse_lds)[QT] = reinterpret_cast<float (*)[QT]>(lsedi_base);
   float (*di_lds)[QT] = reinterpret_cast<float (*)[QT]>(lsedi_base + 2 * QT);
@@ -803,16 +870,12 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
   if (WINDOWED)
     qstop = min(sq, kvblk * KBW + KBW - 1 - off + window);
 
-  // staged registers: q rows, transposed image of (dV: dO / dK: Q),
-  // dO rows (dK phase only)
+  // staged registers: q rows and dO rows.  The dV phase reads the dO image
+  // only by columns, the dK phase reads it by rows and the q image both ways
   bf16x8 qst[QPT], dost[QPT];
-  ushort8 ttst[QPT];
   float lse_st, di_st;
-  const __bf16* tsrc = DKPH ? q : dout;  // transposed-image source
   const long do_base = oa.base(q_base);
   const int do_stride = oa.stride(q_stride);
-  const long t_base = DKPH ? q_base : do_base;
-  const int t_stride = DKPH ? q_stride : do_stride;
 
   auto stage_load = [&](int qt0) {
     const bool full = (qt0 + QT <= sq);
@@ -820,40 +883,17 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
     for (int p = 0; p < QPT; ++p) {
       const int idx = tid + p * 512;
       if (idx >= QT * D / 8) break;
-      const int row = idx / (D / 8);
-      const int c8 = (idx - row * (D / 8)) * 8;
+      int row, ch;
+      stage_map<D>(tid, p, row, ch);
       const int qg = full ? qt0 + row : min(qt0 + row, sq - 1);
       qst[p] = *reinterpret_cast<const bf16x8*>(
-          q + q_base + (long)qg * q_stride + c8);
-      if (DKPH)
-        dost[p] = *reinterpret_cast<const bf16x8*>(
-            dout + do_base + (long)qg * do_stride + c8);
+          q + q_base + (long)qg * q_stride + ch * 8);
+      dost[p] = *reinterpret_cast<const bf16x8*>(
+          dout + do_base + (long)qg * do_stride + ch * 8);
       if (!full && qt0 + row >= sq) {
         qst[p] = (bf16x8)(__bf16(0.f));
-        if (DKPH) dost[p] = (bf16x8)(__bf16(0.f));
+        dost[p] = (bf16x8)(__bf16(0.f));
       }
-    }
-#pragma unroll
-    for (int p = 0; p < QPT; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= D * QT / 8) break;
-      const int c = idx & (D - 1);
-      const int qc = (idx / D) * 8;
-      const unsigned short* tb = reinterpret_cast<const unsigned short*>(
-          tsrc + t_base) + c;
-      ushort8 t8;
-      if (full) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          t8[j] = tb[(long)(qt0 + qc + j) * t_stride];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          unsigned short a = tb[(long)min(qt0 + qc + j, sq - 1) * t_stride];
-          t8[j] = qt0 + qc + j < sq ? a : (unsigned short)0;
-        }
-      }
-      ttst[p] = t8;
     }
     if (tid < QT) {
       const int qg = qt0 + tid;
@@ -863,25 +903,15 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
   };
   auto stage_write = [&](int buf) {
     __bf16* q_lds = smem + buf * BUFSZ;
-    __bf16* t_lds = q_lds + QT * QROW;
-    __bf16* do_lds = t_lds + D * TROW;
+    __bf16* do_lds = q_lds + QT * D;
 #pragma unroll
     for (int p = 0; p < QPT; ++p) {
       const int idx = tid + p * 512;
       if (idx >= QT * D / 8) break;
-      const int row = idx / (D / 8);
-      const int c8 = (idx - row * (D / 8)) * 8;
-      *reinterpret_cast<bf16x8*>(q_lds + row * QROW + c8) = qst[p];
-      if (DKPH)
-        *reinterpret_cast<bf16x8*>(do_lds + row * QROW + c8) = dost[p];
-    }
-#pragma unroll
-    for (int p = 0; p < QPT; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= D * QT / 8) break;
-      const int c = idx & (D - 1);
-      const int qc = (idx / D) * 8;
-      *reinterpret_cast<ushort8*>(t_lds + c * TROW + qc) = ttst[p];
+      int row, ch;
+      stage_map<D>(tid, p, row, ch);
+      *reinterpret_cast<bf16x8*>(q_lds + tile_off<D>(row, ch)) = qst[p];
+      *reinterpret_cast<bf16x8*>(do_lds + tile_off<D>(row, ch)) = dost[p];
     }
     if (tid < QT) {
       lse_lds[buf][tid] = lse_st;
@@ -897,8 +927,8 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
   for (int qt0 = qstart; qt0 < qstop; qt0 += QT) {
     const bool have_next = qt0 + QT < qstop;
     const __bf16* q_lds = smem + cur * BUFSZ;
-    const __bf16* t_lds = q_lds + QT * QROW;
-    const __bf16* do_lds = t_lds + D * TROW;
+    const __bf16* do_lds = q_lds + QT * D;
+    const __bf16* t_lds = DKPH ? q_lds : do_lds;  // read by columns
     if (have_next) stage_load(qt0 + QT);
 
     // two 32-q mfma halves per staged tile
@@ -915,12 +945,10 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
       f32x16 s_acc = (f32x16)(0.f), dp_acc = (f32x16)(0.f);
 #pragma unroll
       for (int ks = 0; ks < NK; ++ks) {
-        bf16x8 qa = *reinterpret_cast<const bf16x8*>(
-            q_lds + (qh * 32 + col) * QROW + ks * 16 + 8 * hi);
+        bf16x8 qa = tile_row_frag<D>(q_lds, qh * 32, ks, lane);
         s_acc = mfma32_bf16(qa, kfr[ks], s_acc);
         if (DKPH) {
-          bf16x8 doa = *reinterpret_cast<const bf16x8*>(
-              do_lds + (qh * 32 + col) * QROW + ks * 16 + 8 * hi);
+          bf16x8 doa = tile_row_frag<D>(do_lds, qh * 32, ks, lane);
           dp_acc = mfma32_bf16(doa, vfr[ks], dp_acc);
         }
       }
@@ -991,8 +1019,7 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
         for (int g = 0; g < 4; ++g) fb.u[g] = w[kh * 4 + g];
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) {
-          bf16x8 ta = *reinterpret_cast<const bf16x8*>(
-              t_lds + (col + 32 * dt) * TROW + qh * 32 + kh * 16 + 8 * hi);
+          bf16x8 ta = tile_tr_frag<D>(t_lds, qh * 32 + kh * 16, dt, lane);
           acc[dt] = mfma32_bf16(ta, fb.f, acc[dt]);
         }
       }
@@ -1011,8 +1038,9 @@ void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        outr[dt * 32 + mfma32_d_row(lane, r)] = (__bf16)acc[dt][r];
+      for (int g = 0; g < 4; ++g)
+        store_d_quad(outr, dt, g, hi, acc[dt][4 * g], acc[dt][4 * g + 1],
+                     acc[dt][4 * g + 2], acc[dt][4 * g + 3]);
   }
 }
 
@@ -1056,8 +1084,8 @@ void flash_bwd_dkv_kernel(const __bf16* __restrict__ dout,
                           bool paired = true, bool sbhd = false,
                           int window = 0) {
   constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  // dK phase is the larger LDS user: q rows + dO rows + transposed image
-  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  // q rows + dO rows per buffer, both phases
+  constexpr int BUFSZ = 2 * QT * D;
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   __shared__ __align__(16) float lsedi[4 * QT];
   const int bh = blockIdx.y;
@@ -1161,7 +1189,7 @@ void flash_varlen_fwd_kernel(const __bf16* __restrict__ q,
                              int hq, int hkv, float scale, bool causal,
                              bool sbhd) {
   constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
   // workgroup-uniform, before any barrier; also covers len == 0
@@ -1185,7 +1213,7 @@ void flash_varlen_bwd_dq_kernel(const __bf16* __restrict__ dout,
                                 int hq, int hkv, float scale, bool causal,
                                 bool sbhd) {
   constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
   if ((int)blockIdx.x * QBF >= g.len) return;
@@ -1208,7 +1236,7 @@ void flash_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
                                  int hq, int hkv, float scale, bool causal,
                                  bool sbhd) {
   constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  constexpr int BUFSZ = 2 * QT * D;
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   __shared__ __align__(16) float lsedi[4 * QT];
   const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
@@ -1284,7 +1312,7 @@ void flash_packed_fwd_kernel(const __bf16* __restrict__ qkv,
                              int b, int s, int G, int qpg, float scale,
                              bool causal, bool paired) {
   constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const PackedHead p = packed_head<D>(b, s, G, qpg);
   const __bf16* k = qkv + (long)qpg * D;
@@ -1317,7 +1345,7 @@ void flash_packed_bwd_dq_kernel(const __bf16* __restrict__ dout,
                                 int G, int qpg, float scale, bool causal,
                                 bool paired) {
   constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const PackedHead p = packed_head<D>(b, s, G, qpg);
   const __bf16* k = qkv + (long)qpg * D;
@@ -1349,7 +1377,7 @@ void flash_packed_bwd_dkv_kernel(const __bf16* __restrict__ dout,
                                  int G, int qpg, float scale, bool causal,
                                  bool paired) {
   constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  constexpr int BUFSZ = 2 * QT * D;
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   __shared__ __align__(16) float lsedi[4 * QT];
   const PackedHead p = packed_head<D>(b, s, G, qpg);
@@ -1442,7 +1470,7 @@ void flash_packed_varlen_fwd_kernel(const __bf16* __restrict__ qkv,
                                     int G, int qpg, float scale,
                                     bool causal) {
   constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
   // workgroup-uniform, before any barrier; also covers len == 0
@@ -1468,7 +1496,7 @@ void flash_packed_varlen_bwd_dq_kernel(const __bf16* __restrict__ dout,
                                        int s, int G, int qpg, float scale,
                                        bool causal) {
   constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * (D + 8) + D * (KB + 8);
+  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
   if ((int)blockIdx.x * QBF >= p.len) return;
@@ -1493,7 +1521,7 @@ void flash_packed_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
                                         int s, int G, int qpg, float scale,
                                         bool causal) {
   constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  constexpr int BUFSZ = 2 * QT * (D + 8) + D * (QT + 8);
+  constexpr int BUFSZ = 2 * QT * D;
   __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
   __shared__ __align__(16) float lsedi[4 * QT];
   const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
