@@ -12,6 +12,8 @@
 #include <tuple>
 #include <vector>
 
+#include "flash_attn_launch.h"
+
 // ---- launcher prototypes (defined in the sibling .hip TUs) ----------------
 template <typename T>
 void rmsnorm_fwd_launch_t(const T*, const T*, T*, float*, long, int, float, hipStream_t, const T* res = nullptr, T* sum_out = nullptr);
@@ -51,20 +53,10 @@ typedef float f32_t;
 DECL_MOE(bf16_t)
 DECL_MOE(f32_t)
 
-void flash_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, bool sbhd = false, int window = 0);
-void attn_di_launch(const __bf16*, const __bf16*, float*, int, int, int, int, hipStream_t, bool sbhd = false);
-void flash_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, int, float, bool, hipStream_t, const __bf16* bias = nullptr, float* dbias = nullptr, bool sbhd = false, int window = 0);
-void flash_varlen_fwd_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
-void flash_varlen_bwd_launch(const __bf16*, const __bf16*, const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, const int*, int, int, int, int, int, int, int, float, bool, bool, hipStream_t);
-void flash_packed_fwd_launch(const __bf16*, __bf16*, float*, int, int, int, int, int, float, bool, hipStream_t);
-void flash_packed_bwd_launch(const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, int, int, int, int, int, float, bool, hipStream_t);
-void flash_packed_varlen_fwd_launch(const __bf16*, __bf16*, float*, const int*, int, int, int, int, int, int, int, float, bool, hipStream_t);
-void flash_packed_varlen_bwd_launch(const __bf16*, const __bf16*, const float*, const float*, __bf16*, __bf16*, __bf16*, const int*, int, int, int, int, int, int, int, float, bool, hipStream_t);
 void rope_qkv_launch(__bf16*, const float*, const float*, long, int, int, int, hipStream_t);
 void qkv_grad_finish_launch(__bf16*, const __bf16*, const __bf16*, const float*, const float*, long, int, int, int, hipStream_t);
 int multi_sumsq_grid(int);
 void multi_sumsq_launch(const long*, int, float*, hipStream_t);
-void mfma_probe_launch(const __bf16*, const __bf16*, float*, bool, hipStream_t);
 void decode_attn_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, int, float, const int*, hipStream_t);
 
 namespace {
@@ -393,36 +385,115 @@ Tensor rope_fwd(const Tensor& x, const Tensor& cos_t, const Tensor& sin_t,
 }
 
 // ---- flash attention ------------------------------------------------------
+// What the eight flash bindings share.  FlashDims is the geometry of a
+// call, read from q/k/v or from a packed linear_qkv buffer.
+struct FlashDims {
+  int b, sq, skv, hq, hkv, d;
+};
+
+// q [b,sq,hq,d], k/v [b,skv,hkv,d] ([s,b,h,d] with sbhd), all checked.
+FlashDims flash_dims(const Tensor& q, const Tensor& k, const Tensor& v,
+                     bool sbhd, const char* who) {
+  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
+  TORCH_CHECK(is_bf16(q), who, ": q: bf16 only on the native path");
+  TORCH_CHECK(q.dim() == 4, who,
+              ": q must be [b,s,h,d] (or [s,b,h,d] with sbhd)");
+  const int bdim = sbhd ? 1 : 0;
+  TORCH_CHECK(is_bf16(k) && k.dim() == 4 && k.size(bdim) == q.size(bdim) &&
+              k.size(3) == q.size(3), who,
+              ": k must be bf16, 4-D, with q's batch and head dim, got ",
+              k.scalar_type(), " ", k.sizes());
+  TORCH_CHECK(is_bf16(v) && v.sizes() == k.sizes(), who,
+              ": v must be bf16 and shaped like k, got ", v.scalar_type(),
+              " ", v.sizes());
+  FlashDims g;
+  g.b = q.size(bdim); g.sq = q.size(1 - bdim);
+  g.hq = q.size(2); g.d = q.size(3);
+  g.skv = k.size(1 - bdim); g.hkv = k.size(2);
+  TORCH_CHECK(g.d == 64 || g.d == 128, who, ": head dim must be 64|128");
+  TORCH_CHECK(g.hkv > 0 && g.hq % g.hkv == 0, who,
+              ": GQA needs hq % hkv == 0");
+  return g;
+}
+
+// Packed-document attention: cu_seqlens [nseg+1] int32 token offsets into
+// the batch-major flattened [b*s] stream.  The values are NOT read on the
+// host (no sync): the caller validates its host copy (they must tile
+// [0, b*s) without straddling a row, with every length <= max_seqlen), so
+// every output row is written exactly once and at::empty is correct.
+// x: the tensor whose device the table must share.
+void check_cu(const Tensor& cu, int64_t max_seqlen, const Tensor& x,
+              const FlashDims& g, const char* who) {
+  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() &&
+              cu.scalar_type() == at::kInt && cu.dim() == 1 &&
+              cu.numel() >= 2 && cu.device() == x.device(), who,
+              ": cu_seqlens must be a contiguous 1-D int32 tensor on the "
+              "inputs' device with at least 2 entries");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= g.sq, who,
+              ": need 1 <= max_seqlen <= s");
+  TORCH_CHECK((int64_t)g.b * g.sq < (1LL << 31), who,
+              ": b*s must fit int32");
+  TORCH_CHECK((cu.numel() - 1) * (int64_t)g.hq <= 65535, who,
+              ": nseg*hq exceeds the grid limit (65535)");
+}
+
+// Backward inputs: dout and o bf16 shaped like the forward's output, lse
+// fp32 [b, hq, sq] on the GPU.  -> lse, contiguous.
+Tensor check_bwd(const Tensor& dout, const Tensor& o, const Tensor& lse,
+                 at::IntArrayRef out_sizes, const FlashDims& g,
+                 const char* who) {
+  CHECK_GPU(dout); CHECK_GPU(o);
+  TORCH_CHECK(is_bf16(dout) && dout.sizes() == out_sizes, who,
+              ": dout/o must be bf16 ", out_sizes, ": dout is ",
+              dout.scalar_type(), " ", dout.sizes());
+  TORCH_CHECK(is_bf16(o) && o.sizes() == out_sizes, who,
+              ": dout/o must be bf16 ", out_sizes, ": o is ", o.scalar_type(),
+              " ", o.sizes());
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+              lse.dim() == 3 && lse.size(0) == g.b && lse.size(1) == g.hq &&
+              lse.size(2) == g.sq, who,
+              ": lse must be fp32 [b, hq, s] on the GPU, got ",
+              lse.scalar_type(), " ", lse.sizes(), " on ", lse.device());
+  return lse.contiguous();
+}
+
+// di = rowsum(dout * o), [b, hq, sq] fp32
+Tensor flash_di(const Tensor& dout, const Tensor& o, const FlashDims& g,
+                bool sbhd) {
+  auto di = at::empty({g.b, g.hq, g.sq}, o.options().dtype(at::kFloat));
+  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), g.b, g.sq, g.hq,
+                 g.d, cur_stream(), sbhd);
+  return di;
+}
+
+// dk_exp / dv_exp carry hq heads: sum each GQA group down to its kv head
+Tensor gqa_sum(const Tensor& exp, const FlashDims& g) {
+  if (g.hq == g.hkv) return exp;
+  return exp.view({exp.size(0), exp.size(1), g.hkv, g.hq / g.hkv, g.d})
+      .sum(3);
+}
+
 std::tuple<Tensor, Tensor> flash_attn_fwd(
     const Tensor& q, const Tensor& k, const Tensor& v, bool causal,
     double scale, const c10::optional<Tensor>& bias = c10::nullopt,
     bool sbhd = false, int64_t window = 0) {
   TORCH_CHECK(window == 0 || causal,
               "flash_attn: sliding window requires causal");
-  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
-  TORCH_CHECK(is_bf16(q), "flash_attn: bf16 only on the native path");
-  TORCH_CHECK(q.dim() == 4, "flash_attn: q must be [b,s,h,d] (or [s,b,h,d] with sbhd)");
-  const int b = sbhd ? q.size(1) : q.size(0);
-  const int sq = sbhd ? q.size(0) : q.size(1);
-  const int hq = q.size(2), d = q.size(3);
-  const int skv = sbhd ? k.size(0) : k.size(1);
-  const int hkv = k.size(2);
-  TORCH_CHECK(d == 64 || d == 128, "flash_attn: head dim must be 64|128");
-  TORCH_CHECK(hq % hkv == 0, "flash_attn: GQA needs hq % hkv == 0");
+  const FlashDims g = flash_dims(q, k, v, sbhd, "flash_attn");
   const __bf16* bp = nullptr;
   Tensor bias_c;
   if (bias.has_value()) {
     bias_c = bias->contiguous();
     TORCH_CHECK(is_bf16(bias_c) && bias_c.dim() == 3 &&
-                bias_c.size(0) == hq && bias_c.size(1) == sq &&
-                bias_c.size(2) == skv,
+                bias_c.size(0) == g.hq && bias_c.size(1) == g.sq &&
+                bias_c.size(2) == g.skv,
                 "flash_attn: bias must be bf16 [hq, sq, skv]");
     bp = bfp(bias_c);
   }
   auto o = at::empty_like(q);
-  auto lse = at::empty({b, hq, sq}, q.options().dtype(at::kFloat));
+  auto lse = at::empty({g.b, g.hq, g.sq}, q.options().dtype(at::kFloat));
   flash_fwd_launch(bfp(q), bfp(k), bfp(v), bfp_mut(o),
-                   lse.data_ptr<float>(), b, sq, skv, hq, hkv, d,
+                   lse.data_ptr<float>(), g.b, g.sq, g.skv, g.hq, g.hkv, g.d,
                    (float)scale, causal, cur_stream(), bp, sbhd,
                    (int)window);
   return {o, lse};
@@ -435,102 +506,59 @@ std::vector<Tensor> flash_attn_bwd(
     int64_t window = 0) {
   TORCH_CHECK(window == 0 || causal,
               "flash_attn_bwd: sliding window requires causal");
-  CHECK_GPU(dout); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o);
-  const int b = sbhd ? q.size(1) : q.size(0);
-  const int sq = sbhd ? q.size(0) : q.size(1);
-  const int hq = q.size(2), d = q.size(3);
-  const int skv = sbhd ? k.size(0) : k.size(1);
-  const int hkv = k.size(2);
-  auto lsec = lse.contiguous();
-  auto di = at::empty({b, hq, sq}, q.options().dtype(at::kFloat));
-  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, sq, hq, d,
-                 cur_stream(), sbhd);
+  const FlashDims g = flash_dims(q, k, v, sbhd, "flash_attn_bwd");
+  auto lsec = check_bwd(dout, o, lse, q.sizes(), g, "flash_attn_bwd");
+  auto di = flash_di(dout, o, g, sbhd);
   auto dq = at::empty_like(q);
-  auto dk_exp = sbhd ? at::empty({skv, b, hq, d}, k.options())
-                     : at::empty({b, skv, hq, d}, k.options());
-  auto dv_exp = sbhd ? at::empty({skv, b, hq, d}, v.options())
-                     : at::empty({b, skv, hq, d}, v.options());
+  auto dk_exp = sbhd ? at::empty({g.skv, g.b, g.hq, g.d}, k.options())
+                     : at::empty({g.b, g.skv, g.hq, g.d}, k.options());
+  auto dv_exp = at::empty_like(dk_exp);
   const __bf16* bp = nullptr;
   float* dbp = nullptr;
   Tensor bias_c, dbias;
   if (bias.has_value()) {
     bias_c = bias->contiguous();
     TORCH_CHECK(is_bf16(bias_c) && bias_c.dim() == 3 &&
-                bias_c.size(0) == hq && bias_c.size(1) == sq &&
-                bias_c.size(2) == skv,
+                bias_c.size(0) == g.hq && bias_c.size(1) == g.sq &&
+                bias_c.size(2) == g.skv,
                 "flash_attn_bwd: bias must be bf16 [hq, sq, skv]");
     bp = bfp(bias_c);
-    dbias = at::zeros({hq, sq, skv}, q.options().dtype(at::kFloat));
+    dbias = at::zeros({g.hq, g.sq, g.skv}, q.options().dtype(at::kFloat));
     dbp = dbias.data_ptr<float>();
   }
   flash_bwd_launch(bfp(dout), bfp(q), bfp(k), bfp(v),
                    lsec.data_ptr<float>(), di.data_ptr<float>(),
-                   bfp_mut(dq), bfp_mut(dk_exp), bfp_mut(dv_exp), b, sq, skv,
-                   hq, hkv, d, (float)scale, causal, cur_stream(), bp, dbp,
-                   sbhd, (int)window);
-  Tensor dk = dk_exp, dv = dv_exp;
-  if (hq != hkv) {
-    const int rep = hq / hkv;
-    if (sbhd) {
-      dk = dk_exp.view({skv, b, hkv, rep, d}).sum(3);
-      dv = dv_exp.view({skv, b, hkv, rep, d}).sum(3);
-    } else {
-      dk = dk_exp.view({b, skv, hkv, rep, d}).sum(3);
-      dv = dv_exp.view({b, skv, hkv, rep, d}).sum(3);
-    }
-  }
+                   bfp_mut(dq), bfp_mut(dk_exp), bfp_mut(dv_exp), g.b, g.sq,
+                   g.skv, g.hq, g.hkv, g.d, (float)scale, causal,
+                   cur_stream(), bp, dbp, sbhd, (int)window);
   if (bias.has_value())
-    return {dq, dk, dv, dbias};
-  return {dq, dk, dv};
+    return {dq, gqa_sum(dk_exp, g), gqa_sum(dv_exp, g), dbias};
+  return {dq, gqa_sum(dk_exp, g), gqa_sum(dv_exp, g)};
 }
 
-// Packed-document self-attention: cu_seqlens [nseg+1] int32 token offsets
-// into the batch-major flattened [b*s] stream.  The values are NOT read on
-// the host (no sync): the caller validates its host copy (they must tile
-// [0, b*s) without straddling a row, with every length <= max_seqlen), so
-// every output row is written exactly once and at::empty is correct.
-void check_varlen(const Tensor& q, const Tensor& k, const Tensor& v,
-                  const Tensor& cu, int64_t max_seqlen, bool sbhd,
-                  const char* who) {
-  TORCH_CHECK(is_bf16(q) && is_bf16(k) && is_bf16(v), who,
-              ": bf16 only on the native path");
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, who,
-              ": q/k/v must be [b,s,h,d] (or [s,b,h,d] with sbhd)");
-  const int64_t s = sbhd ? q.size(0) : q.size(1);
-  const int64_t b = sbhd ? q.size(1) : q.size(0);
-  const int64_t hq = q.size(2), d = q.size(3), hkv = k.size(2);
-  TORCH_CHECK(d == 64 || d == 128, who, ": head dim must be 64|128");
-  TORCH_CHECK(hkv > 0 && hq % hkv == 0, who, ": GQA needs hq % hkv == 0");
-  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0) &&
-              k.size(1) == q.size(1) && k.size(3) == d, who,
+// self-attention only: k/v share q's b and s
+FlashDims varlen_dims(const Tensor& q, const Tensor& k, const Tensor& v,
+                      const Tensor& cu, int64_t max_seqlen, bool sbhd,
+                      const char* who) {
+  const FlashDims g = flash_dims(q, k, v, sbhd, who);
+  TORCH_CHECK(g.skv == g.sq, who,
               ": self-attention only (k/v must match q's b, s and d)");
-  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() &&
-              cu.scalar_type() == at::kInt && cu.dim() == 1 &&
-              cu.numel() >= 2 && cu.device() == q.device(), who,
-              ": cu_seqlens must be a contiguous 1-D int32 tensor on q's "
-              "device with at least 2 entries");
-  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= s, who,
-              ": need 1 <= max_seqlen <= s");
-  TORCH_CHECK(b * s < (1LL << 31), who, ": b*s must fit int32");
-  TORCH_CHECK((cu.numel() - 1) * hq <= 65535, who,
-              ": nseg*hq exceeds the grid limit (65535)");
+  check_cu(cu, max_seqlen, q, g, who);
+  return g;
 }
 
 std::tuple<Tensor, Tensor> flash_attn_varlen_fwd(
     const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu,
     int64_t max_seqlen, bool causal, double scale, bool sbhd = false) {
-  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
-  check_varlen(q, k, v, cu, max_seqlen, sbhd, "flash_attn_varlen_fwd");
-  const int b = sbhd ? q.size(1) : q.size(0);
-  const int s = sbhd ? q.size(0) : q.size(1);
-  const int hq = q.size(2), d = q.size(3), hkv = k.size(2);
-  const int nseg = cu.numel() - 1;
+  const FlashDims g =
+      varlen_dims(q, k, v, cu, max_seqlen, sbhd, "flash_attn_varlen_fwd");
   auto o = at::empty_like(q);
-  auto lse = at::empty({b, hq, s}, q.options().dtype(at::kFloat));
+  auto lse = at::empty({g.b, g.hq, g.sq}, q.options().dtype(at::kFloat));
   flash_varlen_fwd_launch(bfp(q), bfp(k), bfp(v), bfp_mut(o),
-                          lse.data_ptr<float>(), cu.data_ptr<int>(), nseg,
-                          (int)max_seqlen, b, s, hq, hkv, d, (float)scale,
-                          causal, sbhd, cur_stream());
+                          lse.data_ptr<float>(), cu.data_ptr<int>(),
+                          (int)cu.numel() - 1, (int)max_seqlen, g.b, g.sq,
+                          g.hq, g.hkv, g.d, (float)scale, causal, sbhd,
+                          cur_stream());
   return {o, lse};
 }
 
@@ -538,45 +566,20 @@ std::vector<Tensor> flash_attn_varlen_bwd(
     const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
     const Tensor& o, const Tensor& lse, const Tensor& cu,
     int64_t max_seqlen, bool causal, double scale, bool sbhd = false) {
-  CHECK_GPU(dout); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o);
-  check_varlen(q, k, v, cu, max_seqlen, sbhd, "flash_attn_varlen_bwd");
-  TORCH_CHECK(is_bf16(dout) && is_bf16(o) && dout.sizes() == q.sizes() &&
-              o.sizes() == q.sizes(),
-              "flash_attn_varlen_bwd: dout/o must be bf16 shaped like q");
-  const int b = sbhd ? q.size(1) : q.size(0);
-  const int s = sbhd ? q.size(0) : q.size(1);
-  const int hq = q.size(2), d = q.size(3), hkv = k.size(2);
-  const int nseg = cu.numel() - 1;
-  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
-              lse.dim() == 3 && lse.size(0) == b && lse.size(1) == hq &&
-              lse.size(2) == s,
-              "flash_attn_varlen_bwd: lse must be fp32 [b, hq, s]");
-  auto lsec = lse.contiguous();
-  auto di = at::empty({b, hq, s}, q.options().dtype(at::kFloat));
-  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, s, hq, d,
-                 cur_stream(), sbhd);
+  const FlashDims g =
+      varlen_dims(q, k, v, cu, max_seqlen, sbhd, "flash_attn_varlen_bwd");
+  auto lsec = check_bwd(dout, o, lse, q.sizes(), g, "flash_attn_varlen_bwd");
+  auto di = flash_di(dout, o, g, sbhd);
   auto dq = at::empty_like(q);
-  auto dk_exp = sbhd ? at::empty({s, b, hq, d}, k.options())
-                     : at::empty({b, s, hq, d}, k.options());
+  auto dk_exp = at::empty_like(q, k.options());
   auto dv_exp = at::empty_like(dk_exp);
   flash_varlen_bwd_launch(bfp(dout), bfp(q), bfp(k), bfp(v),
                           lsec.data_ptr<float>(), di.data_ptr<float>(),
                           bfp_mut(dq), bfp_mut(dk_exp), bfp_mut(dv_exp),
-                          cu.data_ptr<int>(), nseg, (int)max_seqlen, b, s,
-                          hq, hkv, d, (float)scale, causal, sbhd,
-                          cur_stream());
-  Tensor dk = dk_exp, dv = dv_exp;
-  if (hq != hkv) {
-    const int rep = hq / hkv;
-    if (sbhd) {
-      dk = dk_exp.view({s, b, hkv, rep, d}).sum(3);
-      dv = dv_exp.view({s, b, hkv, rep, d}).sum(3);
-    } else {
-      dk = dk_exp.view({b, s, hkv, rep, d}).sum(3);
-      dv = dv_exp.view({b, s, hkv, rep, d}).sum(3);
-    }
-  }
-  return {dq, dk, dv};
+                          cu.data_ptr<int>(), (int)cu.numel() - 1,
+                          (int)max_seqlen, g.b, g.sq, g.hq, g.hkv, g.d,
+                          (float)scale, causal, sbhd, cur_stream());
+  return {dq, gqa_sum(dk_exp, g), gqa_sum(dv_exp, g)};
 }
 
 // ---- packed-QKV attention ---------------------------------------------------
@@ -628,49 +631,93 @@ void rope_qkv_(Tensor qkv, const Tensor& cos_t, const Tensor& sin_t) {
                   (int)qkv.size(3) - 2, (int)qkv.size(4), cur_stream());
 }
 
-// -> o [s, b, hq, d], lse [b, hq, s]
-std::tuple<Tensor, Tensor> flash_attn_qkv_fwd(const Tensor& qkv, bool causal,
-                                              double scale) {
-  check_qkv(qkv, "flash_attn_qkv_fwd");
-  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
-  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
-  auto o = at::empty({s, b, G * qpg, d}, qkv.options());
-  auto lse = at::empty({b, G * qpg, s}, qkv.options().dtype(at::kFloat));
-  flash_packed_fwd_launch(bfp(qkv), bfp_mut(o), lse.data_ptr<float>(), b, s,
-                          G, qpg, d, (float)scale, causal, cur_stream());
+// check_qkv, and with a cu_seqlens table check_cu (see there: the segments
+// tile [0, b*s), so every q-slot row of dqkv and every o / lse row is
+// written exactly once and at::empty is correct).  hkv = G.
+FlashDims qkv_dims(const Tensor& qkv, const Tensor* cu, int64_t max_seqlen,
+                   const char* who) {
+  check_qkv(qkv, who);
+  const int s = qkv.size(0), G = qkv.size(2);
+  const FlashDims g{(int)qkv.size(1), s, s, G * ((int)qkv.size(3) - 2), G,
+                    (int)qkv.size(4)};
+  if (cu != nullptr) check_cu(*cu, max_seqlen, qkv, g, who);
+  return g;
+}
+
+// -> o [s, b, hq, d], lse [b, hq, s]; cu: the packed-document kernels
+std::tuple<Tensor, Tensor> qkv_fwd(const Tensor& qkv, const Tensor* cu,
+                                   int64_t max_seqlen, bool causal,
+                                   double scale, const char* who) {
+  const FlashDims g = qkv_dims(qkv, cu, max_seqlen, who);
+  const int qpg = g.hq / g.hkv;
+  auto o = at::empty({g.sq, g.b, g.hq, g.d}, qkv.options());
+  auto lse = at::empty({g.b, g.hq, g.sq}, qkv.options().dtype(at::kFloat));
+  if (cu == nullptr)
+    flash_packed_fwd_launch(bfp(qkv), bfp_mut(o), lse.data_ptr<float>(), g.b,
+                            g.sq, g.hkv, qpg, g.d, (float)scale, causal,
+                            cur_stream());
+  else
+    flash_packed_varlen_fwd_launch(
+        bfp(qkv), bfp_mut(o), lse.data_ptr<float>(), cu->data_ptr<int>(),
+        (int)cu->numel() - 1, (int)max_seqlen, g.b, g.sq, g.hkv, qpg, g.d,
+        (float)scale, causal, cur_stream());
   return {o, lse};
 }
 
 // -> dqkv (q slots = dq before the inverse rotation, k and v slots NOT yet
 // written), dk_exp, dv_exp [s, b, hq, d].  qkv_grad_finish_ completes dqkv.
-std::vector<Tensor> flash_attn_qkv_bwd(const Tensor& dout, const Tensor& qkv,
-                                       const Tensor& o, const Tensor& lse,
-                                       bool causal, double scale) {
-  check_qkv(qkv, "flash_attn_qkv_bwd");
-  CHECK_GPU(dout); CHECK_GPU(o); CHECK_GPU(lse);
-  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
-  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
-  const int hq = G * qpg;
-  TORCH_CHECK(is_bf16(dout) && is_bf16(o) && o.dim() == 4 &&
-              o.size(0) == s && o.size(1) == b && o.size(2) == hq &&
-              o.size(3) == d && dout.sizes() == o.sizes(),
-              "flash_attn_qkv_bwd: dout/o must be bf16 [s, b, hq, d]");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 &&
-              lse.size(0) == b && lse.size(1) == hq && lse.size(2) == s,
-              "flash_attn_qkv_bwd: lse must be fp32 [b, hq, s]");
-  auto di = at::empty({b, hq, s}, qkv.options().dtype(at::kFloat));
-  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, s, hq, d,
-                 cur_stream(), /*sbhd=*/true);
+std::vector<Tensor> qkv_bwd(const Tensor& dout, const Tensor& qkv,
+                            const Tensor& o, const Tensor& lse,
+                            const Tensor* cu, int64_t max_seqlen, bool causal,
+                            double scale, const char* who) {
+  const FlashDims g = qkv_dims(qkv, cu, max_seqlen, who);
+  const int qpg = g.hq / g.hkv;
+  auto lsec = check_bwd(dout, o, lse, {g.sq, g.b, g.hq, g.d}, g, who);
+  auto di = flash_di(dout, o, g, /*sbhd=*/true);
   // at::empty: the dq kernel writes every q-slot element and
   // qkv_grad_finish_ writes every k- and v-slot element, each exactly once
   auto dqkv = at::empty_like(qkv);
-  auto dk_exp = at::empty({s, b, hq, d}, qkv.options());
-  auto dv_exp = at::empty({s, b, hq, d}, qkv.options());
-  flash_packed_bwd_launch(bfp(dout), bfp(qkv), lse.data_ptr<float>(),
-                          di.data_ptr<float>(), bfp_mut(dqkv),
-                          bfp_mut(dk_exp), bfp_mut(dv_exp), b, s, G, qpg, d,
-                          (float)scale, causal, cur_stream());
+  auto dk_exp = at::empty({g.sq, g.b, g.hq, g.d}, qkv.options());
+  auto dv_exp = at::empty_like(dk_exp);
+  if (cu == nullptr)
+    flash_packed_bwd_launch(bfp(dout), bfp(qkv), lsec.data_ptr<float>(),
+                            di.data_ptr<float>(), bfp_mut(dqkv),
+                            bfp_mut(dk_exp), bfp_mut(dv_exp), g.b, g.sq,
+                            g.hkv, qpg, g.d, (float)scale, causal,
+                            cur_stream());
+  else
+    flash_packed_varlen_bwd_launch(
+        bfp(dout), bfp(qkv), lsec.data_ptr<float>(), di.data_ptr<float>(),
+        bfp_mut(dqkv), bfp_mut(dk_exp), bfp_mut(dv_exp), cu->data_ptr<int>(),
+        (int)cu->numel() - 1, (int)max_seqlen, g.b, g.sq, g.hkv, qpg, g.d,
+        (float)scale, causal, cur_stream());
   return {dqkv, dk_exp, dv_exp};
+}
+
+std::tuple<Tensor, Tensor> flash_attn_qkv_fwd(const Tensor& qkv, bool causal,
+                                              double scale) {
+  return qkv_fwd(qkv, nullptr, 0, causal, scale, "flash_attn_qkv_fwd");
+}
+
+std::vector<Tensor> flash_attn_qkv_bwd(const Tensor& dout, const Tensor& qkv,
+                                       const Tensor& o, const Tensor& lse,
+                                       bool causal, double scale) {
+  return qkv_bwd(dout, qkv, o, lse, nullptr, 0, causal, scale,
+                 "flash_attn_qkv_bwd");
+}
+
+std::tuple<Tensor, Tensor> flash_attn_qkv_varlen_fwd(
+    const Tensor& qkv, const Tensor& cu, int64_t max_seqlen, bool causal,
+    double scale) {
+  return qkv_fwd(qkv, &cu, max_seqlen, causal, scale,
+                 "flash_attn_qkv_varlen_fwd");
+}
+
+std::vector<Tensor> flash_attn_qkv_varlen_bwd(
+    const Tensor& dout, const Tensor& qkv, const Tensor& o, const Tensor& lse,
+    const Tensor& cu, int64_t max_seqlen, bool causal, double scale) {
+  return qkv_bwd(dout, qkv, o, lse, &cu, max_seqlen, causal, scale,
+                 "flash_attn_qkv_varlen_bwd");
 }
 
 // One pass that turns dqkv into the gradient of the linear_qkv output:
@@ -703,79 +750,6 @@ void qkv_grad_finish_(Tensor dqkv, const Tensor& dk_exp, const Tensor& dv_exp,
   qkv_grad_finish_launch(bfp_mut(dqkv), bfp(dk_exp), bfp(dv_exp), cp, sp,
                          groups, per_table_row, (int)dqkv.size(3) - 2,
                          (int)dqkv.size(4), cur_stream());
-}
-
-// ---- packed documents on the packed-QKV buffer ------------------------------
-// check_qkv plus the cu_seqlens checks of check_varlen.  As there, the table
-// is not read on the host: the caller validated its host copy, the segments
-// tile [0, b*s), so every q-slot row of dqkv (and every o / lse row) is
-// written exactly once and at::empty is correct.
-void check_qkv_varlen(const Tensor& qkv, const Tensor& cu, int64_t max_seqlen,
-                      const char* who) {
-  check_qkv(qkv, who);
-  const int64_t s = qkv.size(0), b = qkv.size(1);
-  const int64_t hq = qkv.size(2) * (qkv.size(3) - 2);
-  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() &&
-              cu.scalar_type() == at::kInt && cu.dim() == 1 &&
-              cu.numel() >= 2 && cu.device() == qkv.device(), who,
-              ": cu_seqlens must be a contiguous 1-D int32 tensor on qkv's "
-              "device with at least 2 entries");
-  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= s, who,
-              ": need 1 <= max_seqlen <= s");
-  TORCH_CHECK(b * s < (1LL << 31), who, ": b*s must fit int32");
-  TORCH_CHECK((cu.numel() - 1) * hq <= 65535, who,
-              ": nseg*hq exceeds the grid limit (65535)");
-}
-
-// -> o [s, b, hq, d], lse [b, hq, s]
-std::tuple<Tensor, Tensor> flash_attn_qkv_varlen_fwd(
-    const Tensor& qkv, const Tensor& cu, int64_t max_seqlen, bool causal,
-    double scale) {
-  check_qkv_varlen(qkv, cu, max_seqlen, "flash_attn_qkv_varlen_fwd");
-  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
-  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
-  const int nseg = cu.numel() - 1;
-  auto o = at::empty({s, b, G * qpg, d}, qkv.options());
-  auto lse = at::empty({b, G * qpg, s}, qkv.options().dtype(at::kFloat));
-  flash_packed_varlen_fwd_launch(bfp(qkv), bfp_mut(o), lse.data_ptr<float>(),
-                                 cu.data_ptr<int>(), nseg, (int)max_seqlen,
-                                 b, s, G, qpg, d, (float)scale, causal,
-                                 cur_stream());
-  return {o, lse};
-}
-
-// -> dqkv (q slots = dq before the inverse rotation, k and v slots NOT yet
-// written), dk_exp, dv_exp [s, b, hq, d].  qkv_grad_finish_ completes dqkv.
-std::vector<Tensor> flash_attn_qkv_varlen_bwd(
-    const Tensor& dout, const Tensor& qkv, const Tensor& o, const Tensor& lse,
-    const Tensor& cu, int64_t max_seqlen, bool causal, double scale) {
-  check_qkv_varlen(qkv, cu, max_seqlen, "flash_attn_qkv_varlen_bwd");
-  CHECK_GPU(dout); CHECK_GPU(o); CHECK_GPU(lse);
-  const int s = qkv.size(0), b = qkv.size(1), G = qkv.size(2);
-  const int qpg = qkv.size(3) - 2, d = qkv.size(4);
-  const int hq = G * qpg;
-  const int nseg = cu.numel() - 1;
-  TORCH_CHECK(is_bf16(dout) && is_bf16(o) && o.dim() == 4 &&
-              o.size(0) == s && o.size(1) == b && o.size(2) == hq &&
-              o.size(3) == d && dout.sizes() == o.sizes(),
-              "flash_attn_qkv_varlen_bwd: dout/o must be bf16 [s, b, hq, d]");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 &&
-              lse.size(0) == b && lse.size(1) == hq && lse.size(2) == s,
-              "flash_attn_qkv_varlen_bwd: lse must be fp32 [b, hq, s]");
-  auto lsec = lse.contiguous();
-  auto di = at::empty({b, hq, s}, qkv.options().dtype(at::kFloat));
-  attn_di_launch(bfp(dout), bfp(o), di.data_ptr<float>(), b, s, hq, d,
-                 cur_stream(), /*sbhd=*/true);
-  auto dqkv = at::empty_like(qkv);
-  auto dk_exp = at::empty({s, b, hq, d}, qkv.options());
-  auto dv_exp = at::empty({s, b, hq, d}, qkv.options());
-  flash_packed_varlen_bwd_launch(bfp(dout), bfp(qkv), lsec.data_ptr<float>(),
-                                 di.data_ptr<float>(), bfp_mut(dqkv),
-                                 bfp_mut(dk_exp), bfp_mut(dv_exp),
-                                 cu.data_ptr<int>(), nseg, (int)max_seqlen,
-                                 b, s, G, qpg, d, (float)scale, causal,
-                                 cur_stream());
-  return {dqkv, dk_exp, dv_exp};
 }
 
 // Single-token decode attention against a KV cache (serving path).

@@ -1,455 +1,11 @@
-// CDNA4 MFMA flash attention (forward with LSE, backward) for gfx950.
-//
-// Replaces the reference's FlashAttention-2 CUDA dependency
-// (galvatron/core/runtime/transformer/attention_impl.py:18-108 and the raw
-// _flash_attn_forward/_backward used by ring attention at :561-729).
-// LSE is a first-class output (ring-CP merge needs it).
-//
-// Layout: q [b, sq, hq, D], k/v [b, skv, hkv, D] bf16, GQA (hq % hkv == 0),
-// causal = bottom-right aligned. lse [b, hq, sq] fp32 (natural log).
-//
-// v2 forward structure (guide §B 8-warp ladder, plain HIP):
-//   8 waves x 32 q rows (QB=256/workgroup), KV tiles of 64;
-//   swapped QK^T (S^T = mfma(K, Q^T)) so each lane owns one q column ->
-//   softmax fully in-register (per-lane m/l scalars, exp2 units);
-//   P redistributed to PV fragments by cvt_pk_bf16 + permlane32_swap
-//   (no LDS round-trip); PV computed as O^T = mfma(V^T, P^T) so the
-//   running rescale is a plain per-lane multiply;
-//   V staged by rows like K (16-byte loads -> b128 LDS writes) into a
-//   swizzled image and read transposed with ds_read_b64_tr_b16 (the v1
-//   scalar ds_write_b16 transpose was 14-37% of wave cycles in
-//   SQ_LDS_BANK_CONFLICT; v2 staged a second, transposed image from
-//   strided 2-byte global loads);
-//   async-stage split (T14): next tile's global loads issue before the
-//   current tile's compute, LDS writes land after the barrier;
-//   per-wave causal tile skip.
-// Backward keeps the v1 two-kernel (dq + expanded dkv) structure; K (dq)
-// and Q / dO (dkv) are held once and read both by rows and transposed.
-#include "common.h"
+// Dense flash attention for gfx950: q [b, sq, hq, D], k/v [b, skv, hkv, D]
+// (or [s, b, h, D] with sbhd), bias, sliding window, cross lengths.  The
+// block bodies are in flash_attn_body.h; this module adds the dense
+// kernels, attn_di and the MFMA layout probe.
+#include "flash_attn_body.h"
+#include "flash_attn_launch.h"
 
 namespace {
-
-constexpr int KVB = 32;   // kv tile of the BACKWARD kernels
-constexpr int QB = 128;   // q/key rows per workgroup (backward kernels)
-
-DEV_INLINE float neg_big() { return -1e30f; }
-
-DEV_INLINE unsigned pack_bf16(float lo, float hi) {
-  union { __hip_bfloat162 h2; unsigned u; } cv;
-  cv.h2 = __hip_bfloat162(__float2bfloat16(lo), __float2bfloat16(hi));
-  return cv.u;
-}
-
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-
-// 16 bias values for one 32-key D-layout column: row(r) = 8*(r>>2) +
-// 4*hi + (r&3) — each r-quad is 4 contiguous bf16, so 4 8-byte loads
-// cover the column.  base must be 4-element aligned (callers pass
-// kv0 + 4*hi with kv0 % 32 == 0).  A quad that reaches past the row end is
-// loaded from the row's last 4 elements and shifted down, so that the keys
-// of a row whose length is no multiple of 4 still get their own bias
-// (clamping the quad to a 4-aligned start gave the last limit % 4 keys the
-// bias of earlier ones); what is shifted in belongs to masked keys.
-DEV_INLINE void load_bias16(const __bf16* brow, int base, int limit,
-                            float* out /*16*/) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int idx = base + 8 * g;
-    const int cl = min(idx, max(limit - 4, 0));
-    union { bf16x4 v; unsigned long long u; } b4;
-    b4.v = *reinterpret_cast<const bf16x4*>(brow + cl);
-    b4.u >>= 16 * min(idx - cl, 3);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) out[4 * g + j] = (float)b4.v[j];
-  }
-}
-
-// ---------------------------------------------------------------------------
-// One LDS image per staged [rows][D] tile, read both by rows (ds_read_b128,
-// the first product of every body) and by columns (ds_read_b64_tr_b16, the
-// second product), so no tile is fetched or held twice.
-//
-// tile_off(row, ch) is the element offset of 16-byte chunk ch (0..D/8-1) of
-// row `row`: 8-row x 32-column subtiles of 512 B, the four chunks of a
-// subtile row XORed with bits 2..3 of the row.  The image is dense
-// (rows*D elements, no padding).  By the bank rule (bank = (byte/4) % 64
-// for b128 / b64 / tr reads, % 32 for writes):
-//   row read   lane l reads row l & 31 (+ const), all lanes of a half one
-//              ch.  ds_read_b128 is served in groups of 16 lanes made of
-//              four aligned 4-lane runs (lanes 0-3, 12-15, 20-27 and so
-//              on), i.e. rows 4n..4n+3 for four different n, each n with
-//              its own n & 3: row & 3 picks the 64-byte quarter, the XOR
-//              key n & 3 the slot in it -> 16 distinct slots, conflict-free;
-//   tr read    a 32-lane half holds rows r0..r0+3 (r0 % 4 == 0) x the four
-//              chunks of one subtile = 256 contiguous bytes, conflict-free;
-//   write      8 consecutive lanes hold two rows x four chunks of a subtile
-//              (stage_map) = 128 contiguous bytes, conflict-free.
-// Reads that differ by ks / dt / +32 rows differ by constants (or by the
-// ks&1 bit inside the XOR), so each kind needs two address registers.
-// ---------------------------------------------------------------------------
-#define TILE_FN __host__ __device__ __forceinline__ constexpr
-template <int D>
-TILE_FN int tile_off(int row, int ch) {
-  return 8 * D * (row >> 3) + 256 * (ch >> 2) + 32 * (row & 7) +
-         8 * ((ch & 3) ^ ((row >> 2) & 3));
-}
-
-// staging pack p of thread tid -> (row, chunk): 4 lanes cover 64 B of a
-// row, the next 4 the row below, then the next subtile of the row pair; a
-// wave covers whole rows (D=128: 4, D=64: 8), so the 16-byte global loads
-// stay coalesced.  A thread's packs are 4096/D rows apart in one chunk, so
-// they share their addresses up to a constant.
-template <int D>
-DEV_INLINE void stage_map(int tid, int p, int& row, int& ch) {
-  const int rest = tid >> 3;
-  row = 2 * (rest / (D / 32)) + ((tid >> 2) & 1) + p * (4096 / D);
-  ch = 4 * (rest % (D / 32)) + (tid & 3);
-}
-
-// Offset of a row read, tile_off(rb + col, 2*ks + hi) for lane l (col =
-// l & 31, hi = l >> 5) and rb % 16 == 0, with the constants split off: one
-// lane term, XOR 16 for odd ks.  tile_reads_match_tile_off ties it to
-// tile_off at compile time.
-template <int D>
-TILE_FN int tile_row_off(int lane, int rb, int ks) {
-  const int col = lane & 31, hi = lane >> 5;
-  const int lane_off = 8 * D * (col >> 3) + 32 * (col & 7) +
-                       8 * (hi ^ ((col >> 2) & 3));
-  return (lane_off ^ (16 * (ks & 1))) + D * rb + 256 * (ks >> 1);
-}
-
-// A/B fragment of a row read: T[rb + col][16*ks + 8*hi + j], j = 0..7
-template <int D>
-DEV_INLINE bf16x8 tile_row_frag(const __bf16* t, int rb, int ks, int lane) {
-  return *reinterpret_cast<const bf16x8*>(t + tile_row_off<D>(lane, rb, ks));
-}
-
-// A fragment of the transposed product: lane l (col = l & 31, hi = l >> 5)
-// gets T[row0 + 8*hi + j][32*dt + col], j = 0..7 — what one b128 read of a
-// transposed image would give.  ds_read_b64_tr_b16 serves 16-lane groups:
-// lane 4q+p of a group supplies the address of row q, columns 4p..4p+3 of a
-// 4 x 16 block and lane i receives column i.  Group g = l >> 4 has hi = g>>1
-// and columns 32*dt + 16*(g&1) + (0..15), i.e. chunk 4*dt + 2*(g&1) +
-// (p>>1), half p & 1; the first read takes rows row0 + 8*hi + q (j = 0..3),
-// the second the rows 4 below (j = 4..7).  With row0 % 16 == 0 the XOR key
-// (row >> 2) & 3 is 2*hi for the first read and 2*hi + 1 for the second, so
-// tile_off reduces to one lane term; the second read is 4 rows (128
-// elements) on with the chunk's low bit flipped (XOR 8).
-// Every lane's address is 8-byte aligned and inside the tile.  EXEC must be
-// all ones: call only under wave-uniform control flow.
-template <int D>
-TILE_FN int tile_tr_off(int lane, int row0, int dt, int second) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int hi = g >> 1;
-  const int lane_off = 8 * D * hi + 32 * q + 16 * ((g & 1) ^ hi) + 4 * p;
-  return D * row0 + 256 * dt + (second ? (lane_off ^ 8) + 128 : lane_off);
-}
-
-typedef __attribute__((ext_vector_type(4))) short tr_short4;
-template <int D>
-DEV_INLINE bf16x8 tile_tr_frag(const __bf16* t, int row0, int dt, int lane) {
-  typedef __attribute__((address_space(3))) tr_short4 lds_short4;
-  union { tr_short4 h[2]; bf16x8 f; } u;
-  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (lds_short4*)(t + tile_tr_off<D>(lane, row0, dt, 0)));
-  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (lds_short4*)(t + tile_tr_off<D>(lane, row0, dt, 1)));
-  return u.f;
-}
-
-// The reduced read offsets against tile_off, for every lane, 16-row step,
-// ks and dt of a 64-row tile (the largest staged): the row read is chunk
-// 2*ks + hi of row rb + col; lane 4q+p of group g of the transposed read
-// is half p & 1 of chunk 4*dt + 2*(g&1) + (p>>1) of row row0 + 8*(g>>1) + q
-// (+ 4 for the second read), 8-byte aligned.
-template <int D>
-constexpr bool tile_reads_match_tile_off() {
-  for (int lane = 0; lane < 64; ++lane)
-    for (int r16 = 0; r16 < 64; r16 += 16) {
-      const int col = lane & 31, hi = lane >> 5;
-      for (int ks = 0; ks < D / 16; ++ks)
-        if (tile_row_off<D>(lane, r16, ks) !=
-            tile_off<D>(r16 + col, 2 * ks + hi))
-          return false;
-      const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-      for (int dt = 0; dt < D / 32; ++dt)
-        for (int second = 0; second < 2; ++second) {
-          const int off = tile_tr_off<D>(lane, r16, dt, second);
-          const int row = r16 + 8 * (g >> 1) + q + 4 * second;
-          const int ch = 4 * dt + 2 * (g & 1) + (p >> 1);
-          if (off != tile_off<D>(row, ch) + 4 * (p & 1) || off % 4 != 0)
-            return false;
-        }
-    }
-  return true;
-}
-static_assert(tile_reads_match_tile_off<64>() &&
-                  tile_reads_match_tile_off<128>(),
-              "tile_row_off / tile_tr_off diverge from tile_off");
-
-// four D-layout registers r = 4g..4g+3 are 4 contiguous columns of the
-// lane's output row (mfma32_d_row): one 8-byte store
-DEV_INLINE void store_d_quad(__bf16* row, int dt, int g, int hi, float a,
-                             float b, float c, float d) {
-  bf16x4 pk;
-  pk[0] = (__bf16)a; pk[1] = (__bf16)b; pk[2] = (__bf16)c; pk[3] = (__bf16)d;
-  *reinterpret_cast<bf16x4*>(row + dt * 32 + 8 * g + 4 * hi) = pk;
-}
-
-// Where the o / dout rows of a head live.  The dense and varlen kernels keep
-// them at q's base and row stride (OutLikeQ: an empty tag, nothing is
-// passed and the address arithmetic is unchanged); the packed-QKV kernels
-// read q from the linear_qkv buffer while o / dout stay [s, b, hq, D], so
-// they pass a base and a stride of their own (OutOwn).
-struct OutLikeQ {
-  DEV_INLINE long base(long q_base) const { return q_base; }
-  DEV_INLINE int stride(int q_stride) const { return q_stride; }
-};
-struct OutOwn {
-  long o_base;
-  int o_stride;
-  DEV_INLINE long base(long) const { return o_base; }
-  DEV_INLINE int stride(int) const { return o_stride; }
-};
-
-// ---------------------------------------------------------------------------
-// forward (v2)
-// ---------------------------------------------------------------------------
-template <int D, bool BIASED = false, bool WINDOWED = false,
-          class OA = OutLikeQ>
-__device__ __attribute__((noinline))
-void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
-                     const __bf16* __restrict__ k,
-                     const __bf16* __restrict__ v,
-                     __bf16* __restrict__ o, float* __restrict__ lse,
-                     __bf16* smem_base, long q_base, long kv_base,
-                     long lse_base, int q_stride, int kv_stride, int off,
-                     int sq, int skv, float sl2e, bool causal,
-                     const __bf16* __restrict__ bias = nullptr,
-                     long bias_base = 0, int window = 0, OA oa = OA()) {
-  constexpr int KB = 64;            // kv tile
-  constexpr int QBF = 256;          // q rows per workgroup (8 waves x 32)
-  constexpr int NK = D / 16;        // S^T K-slices
-  constexpr int ND = D / 32;        // 32-wide d tiles of O^T
-  constexpr int KPT = D / 64;       // staging packs per thread (512 thr)
-
-  constexpr int BUFSZ = 2 * KB * D;  // K rows + V rows (tile_off images)
-  __bf16* smem = smem_base;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int col = lane & 31;
-  const int hi = lane >> 5;
-  const int wid = tid >> 6;
-  const int q0w = qblk * QBF + wid * 32;
-
-  // Q fragments (B-operand of S^T): lane holds Q[q0w+col][ks*16 + 8*hi + j]
-  bf16x8 qf[NK];
-  {
-    const int qg = min(q0w + col, sq - 1);
-    const __bf16* qp = q + q_base + (long)qg * q_stride + 8 * hi;
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks)
-      qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-  }
-
-  f32x16 ot[ND];
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) ot[dt] = (f32x16)(0.f);
-  float m_run = neg_big(), l_run = 0.f;
-
-  int kv_end = causal ? min(skv, qblk * QBF + QBF + off) : skv;
-  const int kv_last_w = causal ? min(skv, q0w + 32 + off) : skv;  // wave's own
-  // sliding window (mistral): keys visible to q are [q+off-window+1, q+off];
-  // whole-workgroup start tile + per-wave lower skip + per-element mask
-  int kv_begin = 0;
-  int kv_first_w = 0;
-  if (WINDOWED) {
-    kv_begin = max(0, (qblk * QBF + off - window + 1) / KB * KB);
-    kv_first_w = max(0, q0w + off - window + 1);
-  }
-
-  // staged registers for the next tile
-  bf16x8 kst[KPT], vst[KPT];
-
-  // Guards are hoisted out of the load loops: per-element branches around
-  // staged loads make hipcc wait vmcnt(0) after EACH load (32 serialized
-  // memory round trips per tile, ~13 us/tile measured — guide §5 trap (c)).
-  // Fast path is branch-free; the tail tile loads clamped addresses and
-  // zeroes by value-select.
-  auto stage_load = [&](int kv0) {
-    const bool full = (kv0 + KB <= skv);
-#pragma unroll
-    for (int p = 0; p < KPT; ++p) {
-      int row, ch;
-      stage_map<D>(tid, p, row, ch);
-      const int kg = kv0 + row;
-      if (full) {
-        const long g = kv_base + (long)kg * kv_stride + ch * 8;
-        kst[p] = *reinterpret_cast<const bf16x8*>(k + g);
-        vst[p] = *reinterpret_cast<const bf16x8*>(v + g);
-      } else {
-        const long g = kv_base + (long)min(kg, skv - 1) * kv_stride + ch * 8;
-        bf16x8 tk = *reinterpret_cast<const bf16x8*>(k + g);
-        bf16x8 tv = *reinterpret_cast<const bf16x8*>(v + g);
-        kst[p] = kg < skv ? tk : (bf16x8)(__bf16(0.f));
-        vst[p] = kg < skv ? tv : (bf16x8)(__bf16(0.f));
-      }
-    }
-  };
-  auto stage_write = [&](int buf) {
-    __bf16* k_lds = smem + buf * BUFSZ;
-    __bf16* v_lds = k_lds + KB * D;
-#pragma unroll
-    for (int p = 0; p < KPT; ++p) {
-      int row, ch;
-      stage_map<D>(tid, p, row, ch);
-      *reinterpret_cast<bf16x8*>(k_lds + tile_off<D>(row, ch)) = kst[p];
-      *reinterpret_cast<bf16x8*>(v_lds + tile_off<D>(row, ch)) = vst[p];
-    }
-  };
-
-  stage_load(kv_begin);
-  stage_write(0);
-  __syncthreads();
-  int cur = 0;
-
-  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KB) {
-    const bool have_next = kv0 + KB < kv_end;
-    const __bf16* k_lds = smem + cur * BUFSZ;
-    const __bf16* v_lds = k_lds + KB * D;
-    if (have_next) stage_load(kv0 + KB);  // async: lands at stage_write
-
-    if (kv0 < kv_last_w && kv0 + KB > kv_first_w) {  // per-wave skips
-      // ---- S^T = K Q^T (two 32-key tiles) ----
-      f32x16 st0 = (f32x16)(0.f), st1 = (f32x16)(0.f);
-#pragma unroll
-      for (int ks = 0; ks < NK; ++ks) {
-        bf16x8 k0 = tile_row_frag<D>(k_lds, 0, ks, lane);
-        bf16x8 k1 = tile_row_frag<D>(k_lds, 32, ks, lane);
-        st0 = mfma32_bf16(k0, qf[ks], st0);
-        st1 = mfma32_bf16(k1, qf[ks], st1);
-      }
-
-      // ---- scale (+ additive bias, + mask on straddle/tail tiles) ----
-      float pv[32];
-      const int qg = q0w + col;
-      const __bf16* brow = nullptr;
-      if (BIASED)
-        brow = bias + bias_base + (long)min(qg, sq - 1) * skv;
-      const bool need_mask =
-          (causal && kv0 + KB > q0w + off + 1) || (kv0 + KB > skv) ||
-          (WINDOWED && kv0 < q0w + 32 + off - window + 1);
-      constexpr float LOG2E = 1.4426950408889634f;
-      float bv[32];
-      if (BIASED) {
-        load_bias16(brow, kv0 + 4 * hi, skv, bv);
-        load_bias16(brow, kv0 + 32 + 4 * hi, skv, bv + 16);
-      }
-      if (need_mask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key0 = kv0 + mfma32_d_row(lane, r);
-          float x0 = st0[r] * sl2e, x1 = st1[r] * sl2e;
-          if (BIASED) {
-            x0 += LOG2E * bv[r];
-            x1 += LOG2E * bv[16 + r];
-          }
-          if (key0 >= skv || (causal && key0 > qg + off) ||
-              (WINDOWED && key0 <= qg + off - window)) x0 = neg_big();
-          if (key0 + 32 >= skv || (causal && key0 + 32 > qg + off) ||
-              (WINDOWED && key0 + 32 <= qg + off - window))
-            x1 = neg_big();
-          pv[r] = x0;
-          pv[16 + r] = x1;
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          pv[r] = st0[r] * sl2e + (BIASED ? LOG2E * bv[r] : 0.f);
-          pv[16 + r] = st1[r] * sl2e + (BIASED ? LOG2E * bv[16 + r] : 0.f);
-        }
-      }
-
-      // ---- in-register online softmax (per-lane q column) ----
-      float mt = pv[0];
-#pragma unroll
-      for (int i = 1; i < 32; ++i) mt = fmaxf(mt, pv[i]);
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float mn = fmaxf(m_run, mt);
-      const float alpha = (m_run <= neg_big()) ? 0.f : exp2f(m_run - mn);
-      const bool dead = (mn <= neg_big());
-      float ps = 0.f;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        pv[i] = dead ? 0.f : exp2f(pv[i] - mn);
-        ps += pv[i];
-      }
-      ps += __shfl_xor(ps, 32, 64);
-      l_run = l_run * alpha + ps;
-      m_run = mn;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-
-      // ---- P -> bf16 PV fragments via cvt_pk + permlane32_swap ----
-      // frag[ks] holds P[q=lane][16*ks + 8*hi + j], j=0..7, as 4 u32 words
-      unsigned w[16];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float* pt = pv + 16 * t;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            // pairs (8i+2g, 8i+2g+1) with (8i+2g+4, 8i+2g+5)
-            unsigned a = pack_bf16(pt[8 * i + 2 * g], pt[8 * i + 2 * g + 1]);
-            unsigned bb = pack_bf16(pt[8 * i + 2 * g + 4],
-                                    pt[8 * i + 2 * g + 5]);
-            auto r2 = __builtin_amdgcn_permlane32_swap(a, bb, false, false);
-            // words of frag (2t + i): position 2g -> r2[0], 2g+1... see map
-            w[(2 * t + i) * 4 + g] = r2[0];      // keys (8hi + 2g, +1)
-            w[(2 * t + i) * 4 + 2 + g] = r2[1];  // keys (8hi + 4 + 2g, +1)
-          }
-        }
-      }
-
-      // ---- O^T += V^T P^T ----
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        union { unsigned u[4]; bf16x8 f; } pb;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) pb.u[g] = w[ks * 4 + g];
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) {
-          bf16x8 va = tile_tr_frag<D>(v_lds, ks * 16, dt, lane);
-          ot[dt] = mfma32_bf16(va, pb.f, ot[dt]);
-        }
-      }
-    }
-
-    if (have_next) stage_write(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
-
-  // ---- epilogue: O^T[d][q=lane], per-lane stats ----
-  const int qg = q0w + col;
-  if (qg < sq) {
-    const float invl = l_run > 0.f ? 1.f / l_run : 0.f;
-    __bf16* orow = o + oa.base(q_base) + (long)qg * oa.stride(q_stride);
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        orow[dt * 32 + mfma32_d_row(lane, r)] = (__bf16)(ot[dt][r] * invl);
-    if (hi == 0)
-      lse[lse_base + qg] =
-          l_run > 0.f ? (m_run + log2f(l_run)) * 0.6931471805599453f
-                      : -INFINITY;
-  }
-}
 
 // thin kernel: common indexing + complementary-pair causal load balance
 // (block x runs q blocks {x, nqb-1-x}: constant total KV tiles per block,
@@ -464,9 +20,8 @@ void flash_fwd_kernel(const __bf16* __restrict__ q,
                       bool causal, const __bf16* __restrict__ bias = nullptr,
                       bool paired = true, bool sbhd = false,
                       int window = 0) {
-  constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  constexpr int QBF = FwdTile<D>::QBF;
+  __shared__ __align__(16) __bf16 smem[2 * FwdTile<D>::BUFSZ];
   const int bh = blockIdx.y;
   const int bi = bh / hq;
   const int h = bh - bi * hq;
@@ -538,208 +93,6 @@ __global__ void attn_di_kernel(const __bf16* __restrict__ dout,
   }
 }
 
-// ---------------------------------------------------------------------------
-// backward dQ (v2): same swapped structure as the forward — 8 waves x 32 q
-// rows, per-lane lse/di scalars, dS^T packed to MFMA fragments with
-// cvt_pk + permlane32_swap (no dS LDS round-trip, no per-row stat arrays:
-// the v1 form spilled 34 dwords/lane to scratch).
-// dQ^T[d][q] += K^T dS accumulated in D-layout, epilogue like the forward.
-// ---------------------------------------------------------------------------
-template <int D, bool BIASED = false, bool WINDOWED = false,
-          class OA = OutLikeQ>
-__device__ __attribute__((noinline))
-void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
-                        const __bf16* __restrict__ q,
-                        const __bf16* __restrict__ k,
-                        const __bf16* __restrict__ v,
-                        const float* __restrict__ lse,
-                        const float* __restrict__ di,
-                        __bf16* __restrict__ dq, __bf16* smem_base,
-                        long q_base, long kv_base, long lse_base,
-                        int q_stride, int kv_stride, int off, int sq,
-                        int skv, float scale, bool causal,
-                        const __bf16* __restrict__ bias = nullptr,
-                        long bias_base = 0, int window = 0, OA oa = OA()) {
-  constexpr int KB = 32;         // kv tile
-  constexpr int QBF = 256;       // q rows per workgroup (8 waves x 32)
-  constexpr int NK = D / 16;
-  constexpr int ND = D / 32;
-  constexpr int KPT = (KB * D / 8 + 511) / 512;  // row packs per thread
-
-  constexpr int BUFSZ = 2 * KB * D;  // K rows + V rows (tile_off images)
-  __bf16* smem = smem_base;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int col = lane & 31;
-  const int hi = lane >> 5;
-  const int wid = tid >> 6;
-  const int q0w = qblk * QBF + wid * 32;
-
-  bf16x8 qf[NK], dof[NK];
-  float lse_c, di_c;
-  {
-    const int qg = min(q0w + col, sq - 1);
-    const __bf16* qp = q + q_base + (long)qg * q_stride + 8 * hi;
-    const __bf16* dop = dout + oa.base(q_base) +
-                        (long)qg * oa.stride(q_stride) + 8 * hi;
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-      qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-      dof[ks] = *reinterpret_cast<const bf16x8*>(dop + ks * 16);
-    }
-    const float l0 = lse[lse_base + qg];
-    const float d0 = di[lse_base + qg];
-    const bool live = q0w + col < sq;
-    lse_c = live ? l0 : INFINITY;  // exp(x - inf) = 0 -> dead rows silent
-    di_c = live ? d0 : 0.f;
-  }
-
-  f32x16 dq_acc[ND];
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) dq_acc[dt] = (f32x16)(0.f);
-
-  const int kv_end = causal ? min(skv, qblk * QBF + QBF + off) : skv;
-  const int kv_last_w = causal ? min(skv, q0w + 32 + off) : skv;
-  int kv_begin = 0, kv_first_w = 0;
-  if (WINDOWED) {
-    kv_begin = max(0, (qblk * QBF + off - window + 1) / KB * KB);
-    kv_first_w = max(0, q0w + off - window + 1);
-  }
-
-  bf16x8 kst[KPT], vst_r[KPT];
-
-  auto stage_load = [&](int kv0) {
-    const bool full = (kv0 + KB <= skv);
-#pragma unroll
-    for (int p = 0; p < KPT; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= KB * D / 8) break;
-      int row, ch;
-      stage_map<D>(tid, p, row, ch);
-      const int kg = full ? kv0 + row : min(kv0 + row, skv - 1);
-      kst[p] = *reinterpret_cast<const bf16x8*>(
-          k + kv_base + (long)kg * kv_stride + ch * 8);
-      vst_r[p] = *reinterpret_cast<const bf16x8*>(
-          v + kv_base + (long)kg * kv_stride + ch * 8);
-      if (!full && kv0 + row >= skv) {
-        kst[p] = (bf16x8)(__bf16(0.f));
-        vst_r[p] = (bf16x8)(__bf16(0.f));
-      }
-    }
-  };
-  auto stage_write = [&](int buf) {
-    __bf16* k_lds = smem + buf * BUFSZ;
-    __bf16* v_lds = k_lds + KB * D;
-#pragma unroll
-    for (int p = 0; p < KPT; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= KB * D / 8) break;
-      int row, ch;
-      stage_map<D>(tid, p, row, ch);
-      *reinterpret_cast<bf16x8*>(k_lds + tile_off<D>(row, ch)) = kst[p];
-      *reinterpret_cast<bf16x8*>(v_lds + tile_off<D>(row, ch)) = vst_r[p];
-    }
-  };
-
-  stage_load(kv_begin);
-  stage_write(0);
-  __syncthreads();
-  int cur = 0;
-
-  const float sl2e = scale;  // bwd stays in natural-log units (lse is ln)
-
-  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KB) {
-    const bool have_next = kv0 + KB < kv_end;
-    const __bf16* k_lds = smem + cur * BUFSZ;
-    const __bf16* v_lds = k_lds + KB * D;
-    if (have_next) stage_load(kv0 + KB);
-
-    if (kv0 < kv_last_w && kv0 + KB > kv_first_w) {
-      // S^T = K Q^T ; dP^T = V dO^T
-      f32x16 st = (f32x16)(0.f), dp = (f32x16)(0.f);
-#pragma unroll
-      for (int ks = 0; ks < NK; ++ks) {
-        bf16x8 kb = tile_row_frag<D>(k_lds, 0, ks, lane);
-        st = mfma32_bf16(kb, qf[ks], st);
-        bf16x8 vb = tile_row_frag<D>(v_lds, 0, ks, lane);
-        dp = mfma32_bf16(vb, dof[ks], dp);
-      }
-
-      // dS^T = P^T (dP^T - Di), branchless mask
-      const int qg = q0w + col;
-      const __bf16* brow = nullptr;
-      if (BIASED)
-        brow = bias + bias_base + (long)min(qg, sq - 1) * skv;
-      const bool need_mask =
-          (causal && kv0 + KB > q0w + off + 1) || (kv0 + KB > skv) ||
-          (WINDOWED && kv0 < q0w + 32 + off - window + 1);
-      float dsv[16];
-      float bv[16];
-      if (BIASED)
-        load_bias16(brow, kv0 + 4 * hi, skv, bv);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float sc = st[r] * sl2e;
-        if (BIASED) sc += bv[r];
-        const float e = __expf(sc - lse_c);
-        float pr = e;
-        if (need_mask) {
-          const int key = kv0 + mfma32_d_row(lane, r);
-          const bool ok = key < skv && !(causal && key > qg + off) &&
-                          !(WINDOWED && key <= qg + off - window);
-          pr = ok ? e : 0.f;
-        }
-        dsv[r] = pr * (dp[r] - di_c) * scale;
-      }
-
-      // pack dS^T to MFMA B-fragments (cvt_pk + permlane32_swap)
-      unsigned w[8];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          unsigned a = pack_bf16(dsv[8 * i + 2 * g], dsv[8 * i + 2 * g + 1]);
-          unsigned bb = pack_bf16(dsv[8 * i + 2 * g + 4],
-                                  dsv[8 * i + 2 * g + 5]);
-          auto r2 = __builtin_amdgcn_permlane32_swap(a, bb, false, false);
-          w[i * 4 + g] = r2[0];
-          w[i * 4 + 2 + g] = r2[1];
-        }
-      }
-
-      // dQ^T += K^T dS
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        union { unsigned u[4]; bf16x8 f; } db;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) db.u[g] = w[kh * 4 + g];
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) {
-          bf16x8 ka = tile_tr_frag<D>(k_lds, kh * 16, dt, lane);
-          dq_acc[dt] = mfma32_bf16(ka, db.f, dq_acc[dt]);
-        }
-      }
-    }
-
-    if (have_next) stage_write(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
-
-  // epilogue: dQ^T[d][q=lane]
-  const int qg = q0w + col;
-  if (qg < sq) {
-    __bf16* dqr = dq + q_base + (long)qg * q_stride;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        store_d_quad(dqr, dt, g, hi, dq_acc[dt][4 * g], dq_acc[dt][4 * g + 1],
-                     dq_acc[dt][4 * g + 2], dq_acc[dt][4 * g + 3]);
-  }
-}
-
 template <int D, bool BIASED = false, bool WINDOWED = false>
 __global__ __launch_bounds__(512, 2)
 void flash_bwd_dq_kernel(const __bf16* __restrict__ dout,
@@ -754,9 +107,8 @@ void flash_bwd_dq_kernel(const __bf16* __restrict__ dout,
                          const __bf16* __restrict__ bias = nullptr,
                          bool paired = true, bool sbhd = false,
                          int window = 0) {
-  constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
+  constexpr int QBF = DqTile<D>::QBF;
+  __shared__ __align__(16) __bf16 smem[2 * DqTile<D>::BUFSZ];
   const int bh = blockIdx.y;
   const int bi = bh / hq;
   const int h = bh - bi * hq;
@@ -785,288 +137,6 @@ void flash_bwd_dq_kernel(const __bf16* __restrict__ dout,
   }
 }
 
-// ---------------------------------------------------------------------------
-// backward dK/dV (v5): expanded per q-head (host reduces over the GQA
-// group), 8 waves x 32 keys (256 keys/workgroup), async-staged q tiles.
-//
-// v5 = two SEQUENTIAL phases in one kernel (dV pass, then dK pass), each
-// with only 64 accumulator VGPRs so the wave's K (and V) fragments are
-// PRELOADED into loop-invariant registers.  The v3/v4 single-pass variant
-// kept 128 accumulator VGPRs live (dkt+dvt) and the compiler was forced
-// to re-load every K/V fragment from L2 one at a time with a full
-// vmcnt(0) drain before EACH MFMA — rocprofv3 PMC showed the waves parked
-// (SQ_WAIT_ANY 73.7% of wave cycles, MFMA busy 28%) while the healthy dq
-// kernel sits at 46%/51%.  The S matrix is computed twice (once per
-// phase): +25% MFMA work for register room — measured net win.
-//   phase dV:  S = mfma(Q_frag[from q_lds rows], K^T_frag[kfr regs])
-//              dV^T[d][key] = mfma(dO^T_frag[from t_lds], P_frag[permlane])
-//   phase dK:  S again; dP = mfma(dO_frag[from do_lds rows], V^T[vfr regs])
-//              dK^T[d][key] = mfma(Q^T_frag[from t_lds], dS_frag[permlane])
-// ---------------------------------------------------------------------------
-template <int D, bool DKPH, bool BIASED = false, bool WINDOWED = false,
-          class OA = OutLikeQ>
-__device__ __attribute__((noinline))
-void flash_bwd_dkv_phase(int kvblk, const __bf16* __restrict__ dout,
-                         const __bf16* __restrict__ q,
-                         const __bf16* __restrict__ k,
-                         const __bf16* __restrict__ v,
-                         const float* __restrict__ lse,
-                         const float* __restrict__ di,
-                         __bf16* __restrict__ dk_exp,
-                         __bf16* __restrict__ dv_exp, __bf16* smem_base,
-                         float* lsedi_base, long q_base, long kv_base,
-                         long dkv_base, long lse_base, int q_stride,
-                         int kv_stride, int dkv_stride, int off, int sq,
-                         int skv, float scale, bool causal,
-                         const __bf16* __restrict__ bias = nullptr,
-                         float* __restrict__ dbias = nullptr,
-                         long bias_base = 0, int window = 0, OA oa = OA()) {
-  constexpr int QT = 64;           // q tile (2 mfma halves per stage)
-  constexpr int KBW = 256;         // keys per workgroup (8 waves x 32)
-  constexpr int NK = D / 16;
-  constexpr int ND = D / 32;
-  constexpr int QPT = (QT * D / 8 + 511) / 512;   // row packs per thread
-
-  // LDS per buffer: q rows + dO rows (tile_off images), in both phases
-  constexpr int BUFSZ = 2 * QT * D;
-  __bf16* smem = smem_base;
-  float (*lse_lds)[QT] = reinterpret_cast<float (*)[QT]>(lsedi_base);
-  float (*di_lds)[QT] = reinterpret_cast<float (*)[QT]>(lsedi_base + 2 * QT);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col = lane & 31;   // this wave's key index
-  const int hi = lane >> 5;
-  const int k0w = kvblk * KBW + wid * 32;  // this wave's first key row
-
-  // loop-invariant K (and V) fragments, preloaded into registers — the
-  // whole point of the phase split
-  const int kg_f = min(k0w + col, skv - 1);
-  bf16x8 kfr[NK];
-  bf16x8 vfr[DKPH ? NK : 1];
-  {
-    const __bf16* kp_f = k + kv_base + (long)kg_f * kv_stride + 8 * hi;
-    const __bf16* vp_f = v + kv_base + (long)kg_f * kv_stride + 8 * hi;
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-      kfr[ks] = *reinterpret_cast<const bf16x8*>(kp_f + ks * 16);
-      if (DKPH)
-        vfr[ks] = *reinterpret_cast<const bf16x8*>(vp_f + ks * 16);
-    }
-  }
-
-  f32x16 acc[ND];
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) acc[dt] = (f32x16)(0.f);
-
-  // first q tile that can attend any key of this block (per-wave causal
-  // skipping happens per 32-q half inside the loop); with a sliding
-  // window, also the LAST q that can see any of this block's keys:
-  // q <= key - off + window - 1
-  int qstart = 0;
-  if (causal) qstart = max(0, ((kvblk * KBW - off) / QT) * QT);
-  int qstop = sq;
-  if (WINDOWED)
-    qstop = min(sq, kvblk * KBW + KBW - 1 - off + window);
-
-  // staged registers: q rows and dO rows.  The dV phase reads the dO image
-  // only by columns, the dK phase reads it by rows and the q image both ways
-  bf16x8 qst[QPT], dost[QPT];
-  float lse_st, di_st;
-  const long do_base = oa.base(q_base);
-  const int do_stride = oa.stride(q_stride);
-
-  auto stage_load = [&](int qt0) {
-    const bool full = (qt0 + QT <= sq);
-#pragma unroll
-    for (int p = 0; p < QPT; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= QT * D / 8) break;
-      int row, ch;
-      stage_map<D>(tid, p, row, ch);
-      const int qg = full ? qt0 + row : min(qt0 + row, sq - 1);
-      qst[p] = *reinterpret_cast<const bf16x8*>(
-          q + q_base + (long)qg * q_stride + ch * 8);
-      dost[p] = *reinterpret_cast<const bf16x8*>(
-          dout + do_base + (long)qg * do_stride + ch * 8);
-      if (!full && qt0 + row >= sq) {
-        qst[p] = (bf16x8)(__bf16(0.f));
-        dost[p] = (bf16x8)(__bf16(0.f));
-      }
-    }
-    if (tid < QT) {
-      const int qg = qt0 + tid;
-      lse_st = qg < sq ? lse[lse_base + qg] : INFINITY;
-      if (DKPH) di_st = qg < sq ? di[lse_base + qg] : 0.f;
-    }
-  };
-  auto stage_write = [&](int buf) {
-    __bf16* q_lds = smem + buf * BUFSZ;
-    __bf16* do_lds = q_lds + QT * D;
-#pragma unroll
-    for (int p = 0; p < QPT; ++p) {
-      const int idx = tid + p * 512;
-      if (idx >= QT * D / 8) break;
-      int row, ch;
-      stage_map<D>(tid, p, row, ch);
-      *reinterpret_cast<bf16x8*>(q_lds + tile_off<D>(row, ch)) = qst[p];
-      *reinterpret_cast<bf16x8*>(do_lds + tile_off<D>(row, ch)) = dost[p];
-    }
-    if (tid < QT) {
-      lse_lds[buf][tid] = lse_st;
-      if (DKPH) di_lds[buf][tid] = di_st;
-    }
-  };
-
-  stage_load(qstart);
-  stage_write(0);
-  __syncthreads();
-  int cur = 0;
-
-  for (int qt0 = qstart; qt0 < qstop; qt0 += QT) {
-    const bool have_next = qt0 + QT < qstop;
-    const __bf16* q_lds = smem + cur * BUFSZ;
-    const __bf16* do_lds = q_lds + QT * D;
-    const __bf16* t_lds = DKPH ? q_lds : do_lds;  // read by columns
-    if (have_next) stage_load(qt0 + QT);
-
-    // two 32-q mfma halves per staged tile
-#pragma unroll
-    for (int qh = 0; qh < QT / 32; ++qh) {
-      const int q0h = qt0 + qh * 32;
-      // per-half skips (wave-uniform): any key of this wave live?
-      if (causal && q0h + 31 + off < k0w) continue;
-      if (WINDOWED && q0h + off - window + 1 > k0w + 31) continue;
-      if (q0h >= sq) continue;
-
-      // S = Q K^T (; dP = dO V^T)  D-layout rows=q(crow), cols=key(lane);
-      // A-frag lane l&31 = q row of the half, B-frag lane = key
-      f32x16 s_acc = (f32x16)(0.f), dp_acc = (f32x16)(0.f);
-#pragma unroll
-      for (int ks = 0; ks < NK; ++ks) {
-        bf16x8 qa = tile_row_frag<D>(q_lds, qh * 32, ks, lane);
-        s_acc = mfma32_bf16(qa, kfr[ks], s_acc);
-        if (DKPH) {
-          bf16x8 doa = tile_row_frag<D>(do_lds, qh * 32, ks, lane);
-          dp_acc = mfma32_bf16(doa, vfr[ks], dp_acc);
-        }
-      }
-
-      float wv[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qrow = mfma32_d_row(lane, r);
-        const float lse_r = lse_lds[cur][qh * 32 + qrow];
-        float sc = s_acc[r] * scale;
-        if (BIASED) {
-          const long bq = (long)min(q0h + qrow, sq - 1);
-          sc += (float)bias[bias_base + bq * skv +
-                            min(k0w + col, skv - 1)];
-        }
-        const float e = __expf(sc - lse_r);
-        float p = e;
-        if (WINDOWED) {
-          const int keyg = k0w + col;
-          const int qo = q0h + qrow + off;
-          const bool ok = keyg < skv && (!causal || keyg <= qo) &&
-                          keyg > qo - window;
-          p = ok ? e : 0.f;
-        } else if (causal) {
-          const int keyg = k0w + col;
-          const bool ok = keyg < skv && keyg <= q0h + qrow + off;
-          p = ok ? e : 0.f;
-        } else if (k0w + col >= skv) {
-          p = 0.f;
-        }
-        if (DKPH) {
-          const float di_r = di_lds[cur][qh * 32 + qrow];
-          const float t = p * (dp_acc[r] - di_r);
-          if (BIASED) {
-            // d(bias) = dS (un-scaled); batch contributions accumulate
-            // via fp32 atomics into [hq, sq, skv]
-            const int bq = q0h + qrow, bk = k0w + col;
-            if (bq < sq && bk < skv)
-              atomicAdd(dbias + bias_base + (long)bq * skv + bk, t);
-          }
-          wv[r] = t * scale;
-        } else {
-          wv[r] = p;
-        }
-      }
-
-      // convert P / dS (D-layout rows=q) to B-fragments (lane=key,
-      // in-lane=q) via cvt_pk + permlane32_swap
-      unsigned w[8];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          unsigned a = pack_bf16(wv[8 * i + 2 * g], wv[8 * i + 2 * g + 1]);
-          unsigned bb = pack_bf16(wv[8 * i + 2 * g + 4],
-                                  wv[8 * i + 2 * g + 5]);
-          auto r2 = __builtin_amdgcn_permlane32_swap(a, bb, false, false);
-          w[i * 4 + g] = r2[0];
-          w[i * 4 + 2 + g] = r2[1];
-        }
-      }
-
-      // dV^T += dO^T P  /  dK^T += Q^T dS  (two K=16 slices of the half)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        union { unsigned u[4]; bf16x8 f; } fb;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) fb.u[g] = w[kh * 4 + g];
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) {
-          bf16x8 ta = tile_tr_frag<D>(t_lds, qh * 32 + kh * 16, dt, lane);
-          acc[dt] = mfma32_bf16(ta, fb.f, acc[dt]);
-        }
-      }
-    }
-
-    if (have_next) stage_write(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
-
-  // epilogue: dK^T/dV^T D-layout rows=d(crow), cols=key(lane)
-  const int keyg = k0w + col;
-  if (keyg < skv) {
-    __bf16* outr = (DKPH ? dk_exp : dv_exp) + dkv_base +
-                   (long)keyg * dkv_stride;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        store_d_quad(outr, dt, g, hi, acc[dt][4 * g], acc[dt][4 * g + 1],
-                     acc[dt][4 * g + 2], acc[dt][4 * g + 3]);
-  }
-}
-
-template <int D, bool BIASED = false, bool WINDOWED = false,
-          class OA = OutLikeQ>
-__device__ void flash_bwd_dkv_block(
-    int kvblk, const __bf16* __restrict__ dout, const __bf16* __restrict__ q,
-    const __bf16* __restrict__ k, const __bf16* __restrict__ v,
-    const float* __restrict__ lse, const float* __restrict__ di,
-    __bf16* __restrict__ dk_exp, __bf16* __restrict__ dv_exp,
-    __bf16* smem_base, float* lsedi_base, long q_base, long kv_base,
-    long dkv_base, long lse_base, int q_stride, int kv_stride,
-    int dkv_stride, int off, int sq, int skv, float scale, bool causal,
-    const __bf16* bias = nullptr, float* dbias = nullptr,
-    long bias_base = 0, int window = 0, OA oa = OA()) {
-  flash_bwd_dkv_phase<D, false, BIASED, WINDOWED, OA>(
-      kvblk, dout, q, k, v, lse, di, dk_exp, dv_exp, smem_base, lsedi_base,
-      q_base, kv_base, dkv_base, lse_base, q_stride, kv_stride, dkv_stride,
-      off, sq, skv, scale, causal, bias, dbias, bias_base, window, oa);
-  __syncthreads();
-  flash_bwd_dkv_phase<D, true, BIASED, WINDOWED, OA>(
-      kvblk, dout, q, k, v, lse, di, dk_exp, dv_exp, smem_base, lsedi_base,
-      q_base, kv_base, dkv_base, lse_base, q_stride, kv_stride, dkv_stride,
-      off, sq, skv, scale, causal, bias, dbias, bias_base, window, oa);
-}
-
 template <int D, bool BIASED = false, bool WINDOWED = false>
 __global__ __launch_bounds__(512, 2)
 void flash_bwd_dkv_kernel(const __bf16* __restrict__ dout,
@@ -1083,11 +153,9 @@ void flash_bwd_dkv_kernel(const __bf16* __restrict__ dout,
                           float* __restrict__ dbias = nullptr,
                           bool paired = true, bool sbhd = false,
                           int window = 0) {
-  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  // q rows + dO rows per buffer, both phases
-  constexpr int BUFSZ = 2 * QT * D;
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  __shared__ __align__(16) float lsedi[4 * QT];
+  constexpr int KBW = DkvTile<D>::KBW;
+  __shared__ __align__(16) __bf16 smem[2 * DkvTile<D>::BUFSZ];
+  __shared__ __align__(16) float lsedi[4 * DkvTile<D>::QT];
   const int bh = blockIdx.y;
   const int bi = bh / hq;
   const int h = bh - bi * hq;
@@ -1123,431 +191,6 @@ void flash_bwd_dkv_kernel(const __bf16* __restrict__ dout,
 }
 
 // ---------------------------------------------------------------------------
-// packed-document (varlen) self-attention: the same block bodies, mapped
-// one workgroup per (segment, head, 256-row block).  cu[nseg+1] holds token
-// offsets into the batch-major flattened [b*s] stream; a segment never
-// straddles a batch row, so it is a contiguous run of rows in both layouts
-// and only the bases change.  sq = skv = len, off = 0.  lse/di keep the
-// dense [b, hq, s] layout.  No complementary pairing: blocks past the end
-// of a short segment leave before touching memory, and mixed lengths are
-// left to the hardware scheduler.
-// ---------------------------------------------------------------------------
-//
-// These kernels are compiled in a translation unit of their own
-// (flash_attn_varlen.hip includes this file with GALV_FLASH_VARLEN_TU set).
-// The block bodies are file-local noinline functions whose LDS base the
-// compiler folds to a constant while the dense kernel is their only caller;
-// a second caller in the same module undoes that folding and costs the
-// dense kernels SGPRs and scratch.  In their own module the dense code
-// objects stay exactly as they were.  Here each body has one call site and
-// is inlined into it (off = 0 and sq == skv fold away; no scratch at D=64).
-#ifdef GALV_FLASH_VARLEN_TU
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wignored-attributes"
-#define VARLEN_INLINE_CALL [[clang::always_inline]]
-
-struct VarlenSeg {
-  int len;        // tokens in the segment (0 = nothing to do)
-  long q_base, kv_base, dkv_base, lse_base;
-  int q_str, kv_str, dkv_str;
-};
-
-template <int D>
-DEV_INLINE VarlenSeg varlen_seg(const int* __restrict__ cu, int b, int s,
-                                int hq, int hkv, bool sbhd) {
-  VarlenSeg g;
-  const int seg = blockIdx.y / hq;
-  const int h = blockIdx.y - seg * hq;
-  const int hk = h / (hq / hkv);
-  const int t0 = cu[seg];
-  const int len = cu[seg + 1] - t0;
-  const int bi = t0 / s;
-  const int p0 = t0 - bi * s;
-  // a malformed table (negative offset, past the last row, straddling a
-  // row) maps to "empty" so no address is ever formed from it
-  const bool ok = t0 >= 0 && len > 0 && bi < b && p0 + len <= s;
-  g.len = ok ? len : 0;
-  g.q_base = sbhd ? (((long)p0 * b + bi) * hq + h) * D
-                  : ((long)t0 * hq + h) * D;
-  g.kv_base = sbhd ? (((long)p0 * b + bi) * hkv + hk) * D
-                   : ((long)t0 * hkv + hk) * D;
-  g.dkv_base = g.q_base;  // dk_exp/dv_exp carry hq heads
-  g.q_str = (sbhd ? b * hq : hq) * D;
-  g.kv_str = (sbhd ? b * hkv : hkv) * D;
-  g.dkv_str = g.q_str;
-  g.lse_base = ((long)bi * hq + h) * s + p0;
-  return g;
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_varlen_fwd_kernel(const __bf16* __restrict__ q,
-                             const __bf16* __restrict__ k,
-                             const __bf16* __restrict__ v,
-                             __bf16* __restrict__ o, float* __restrict__ lse,
-                             const int* __restrict__ cu, int b, int s,
-                             int hq, int hkv, float scale, bool causal,
-                             bool sbhd) {
-  constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
-  // workgroup-uniform, before any barrier; also covers len == 0
-  if ((int)blockIdx.x * QBF >= g.len) return;
-  const float sl2e = scale * 1.4426950408889634f;
-  VARLEN_INLINE_CALL flash_fwd_block<D>(
-      blockIdx.x, q, k, v, o, lse, smem, g.q_base, g.kv_base, g.lse_base,
-      g.q_str, g.kv_str, 0, g.len, g.len, sl2e, causal);
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_varlen_bwd_dq_kernel(const __bf16* __restrict__ dout,
-                                const __bf16* __restrict__ q,
-                                const __bf16* __restrict__ k,
-                                const __bf16* __restrict__ v,
-                                const float* __restrict__ lse,
-                                const float* __restrict__ di,
-                                __bf16* __restrict__ dq,
-                                const int* __restrict__ cu, int b, int s,
-                                int hq, int hkv, float scale, bool causal,
-                                bool sbhd) {
-  constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
-  if ((int)blockIdx.x * QBF >= g.len) return;
-  VARLEN_INLINE_CALL flash_bwd_dq_block<D>(
-      blockIdx.x, dout, q, k, v, lse, di, dq, smem, g.q_base, g.kv_base,
-      g.lse_base, g.q_str, g.kv_str, 0, g.len, g.len, scale, causal);
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
-                                 const __bf16* __restrict__ q,
-                                 const __bf16* __restrict__ k,
-                                 const __bf16* __restrict__ v,
-                                 const float* __restrict__ lse,
-                                 const float* __restrict__ di,
-                                 __bf16* __restrict__ dk_exp,
-                                 __bf16* __restrict__ dv_exp,
-                                 const int* __restrict__ cu, int b, int s,
-                                 int hq, int hkv, float scale, bool causal,
-                                 bool sbhd) {
-  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  constexpr int BUFSZ = 2 * QT * D;
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  __shared__ __align__(16) float lsedi[4 * QT];
-  const VarlenSeg g = varlen_seg<D>(cu, b, s, hq, hkv, sbhd);
-  if ((int)blockIdx.x * KBW >= g.len) return;
-  // the two phases of flash_bwd_dkv_block, dV then dK
-  VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, false>(
-      blockIdx.x, dout, q, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
-      g.q_base, g.kv_base, g.dkv_base, g.lse_base, g.q_str, g.kv_str,
-      g.dkv_str, 0, g.len, g.len, scale, causal);
-  __syncthreads();
-  VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, true>(
-      blockIdx.x, dout, q, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
-      g.q_base, g.kv_base, g.dkv_base, g.lse_base, g.q_str, g.kv_str,
-      g.dkv_str, 0, g.len, g.len, scale, causal);
-}
-
-#pragma clang diagnostic pop
-#endif  // GALV_FLASH_VARLEN_TU
-
-// ---------------------------------------------------------------------------
-// packed-QKV self-attention: the same block bodies reading q, k and v
-// straight from the linear_qkv output [s, b, G, qpg+2, D] (G local kv
-// groups; slots 0..qpg-1 of a group are its q heads, slot qpg is k, slot
-// qpg+1 is v), so nothing has to separate them in memory first.  sbhd only,
-// sq = skv = s, off = 0, no bias, no window.
-//   row stride (q, k, v, dq)   b*G*(qpg+2)*D
-//   q / dq head base           ((bi*G + h/qpg)*(qpg+2) + h%qpg)*D
-//   k, v                       slots qpg, qpg+1 of group h/qpg: the k and v
-//                              pointers are pre-offset by qpg*D, (qpg+1)*D
-//                              and share the group base
-// o, dout, dk_exp, dv_exp stay [s, b, hq, D] and lse, di [b, hq, s]; dq is
-// written into the q slots of a dqkv buffer of the packed geometry.  Every
-// offset is a multiple of D, so the 16-byte vector accesses stay aligned.
-//
-// Compiled through flash_attn_qkv.hip for the reason given above for the
-// varlen kernels.  Unlike those, these keep complementary-pair causal
-// scheduling: they run the flagship's shape, where dropping it costs
-// 1.5-1.8x.  dq and dkv keep the dense structure (noinline bodies, two call
-// sites); the forward inlines one copy of its body in a two-pass loop.
-// ---------------------------------------------------------------------------
-#ifdef GALV_FLASH_PACKED_TU
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wignored-attributes"
-
-struct PackedHead {
-  long q_base, kv_base, o_base, lse_base;
-  int qkv_str, o_str;
-};
-
-template <int D>
-DEV_INLINE PackedHead packed_head(int b, int s, int G, int qpg) {
-  PackedHead p;
-  const int hq = G * qpg;
-  const int bh = blockIdx.y;
-  const int bi = bh / hq;
-  const int h = bh - bi * hq;
-  const int g = h / qpg;
-  const int slot = h - g * qpg;
-  const long grp = ((long)bi * G + g) * (qpg + 2);
-  p.q_base = (grp + slot) * D;
-  p.kv_base = grp * D;
-  p.o_base = ((long)bi * hq + h) * D;
-  p.lse_base = ((long)bi * hq + h) * s;
-  p.qkv_str = b * G * (qpg + 2) * D;
-  p.o_str = b * hq * D;
-  return p;
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_packed_fwd_kernel(const __bf16* __restrict__ qkv,
-                             __bf16* __restrict__ o, float* __restrict__ lse,
-                             int b, int s, int G, int qpg, float scale,
-                             bool causal, bool paired) {
-  constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  const PackedHead p = packed_head<D>(b, s, G, qpg);
-  const __bf16* k = qkv + (long)qpg * D;
-  const __bf16* v = k + D;
-  const OutOwn oa{p.o_base, p.o_str};
-  const float sl2e = scale * 1.4426950408889634f;
-  const int nqb = (s + QBF - 1) / QBF;
-  // one inlined copy of the body, run for the block and then for its
-  // complementary partner: out of line (as in the dense kernel) the
-  // compiler serialised the V staging loads of the full-tile path here
-  for (int pass = 0; pass < 2; ++pass) {
-    const int qb = pass == 0 ? (int)blockIdx.x : nqb - 1 - (int)blockIdx.x;
-    if (pass == 1) {
-      if (!(causal && paired && qb > (int)blockIdx.x)) break;
-      __syncthreads();
-    }
-    [[clang::always_inline]] flash_fwd_block<D, false, false, OutOwn>(
-        qb, qkv, k, v, o, lse, smem, p.q_base, p.kv_base, p.lse_base,
-        p.qkv_str, p.qkv_str, 0, s, s, sl2e, causal, nullptr, 0, 0, oa);
-  }
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_packed_bwd_dq_kernel(const __bf16* __restrict__ dout,
-                                const __bf16* __restrict__ qkv,
-                                const float* __restrict__ lse,
-                                const float* __restrict__ di,
-                                __bf16* __restrict__ dqkv, int b, int s,
-                                int G, int qpg, float scale, bool causal,
-                                bool paired) {
-  constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  const PackedHead p = packed_head<D>(b, s, G, qpg);
-  const __bf16* k = qkv + (long)qpg * D;
-  const __bf16* v = k + D;
-  const OutOwn oa{p.o_base, p.o_str};
-  const int nqb = (s + QBF - 1) / QBF;
-  flash_bwd_dq_block<D, false, false, OutOwn>(
-      blockIdx.x, dout, qkv, k, v, lse, di, dqkv, smem, p.q_base, p.kv_base,
-      p.lse_base, p.qkv_str, p.qkv_str, 0, s, s, scale, causal, nullptr, 0,
-      0, oa);
-  const int qb2 = nqb - 1 - (int)blockIdx.x;
-  if (causal && paired && qb2 > (int)blockIdx.x) {
-    __syncthreads();
-    flash_bwd_dq_block<D, false, false, OutOwn>(
-        qb2, dout, qkv, k, v, lse, di, dqkv, smem, p.q_base, p.kv_base,
-        p.lse_base, p.qkv_str, p.qkv_str, 0, s, s, scale, causal, nullptr,
-        0, 0, oa);
-  }
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_packed_bwd_dkv_kernel(const __bf16* __restrict__ dout,
-                                 const __bf16* __restrict__ qkv,
-                                 const float* __restrict__ lse,
-                                 const float* __restrict__ di,
-                                 __bf16* __restrict__ dk_exp,  // [s,b,hq,D]
-                                 __bf16* __restrict__ dv_exp, int b, int s,
-                                 int G, int qpg, float scale, bool causal,
-                                 bool paired) {
-  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  constexpr int BUFSZ = 2 * QT * D;
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  __shared__ __align__(16) float lsedi[4 * QT];
-  const PackedHead p = packed_head<D>(b, s, G, qpg);
-  const __bf16* k = qkv + (long)qpg * D;
-  const __bf16* v = k + D;
-  const OutOwn oa{p.o_base, p.o_str};
-  const int nkb = (s + KBW - 1) / KBW;
-  // dk_exp / dv_exp carry hq heads in o's layout
-  flash_bwd_dkv_block<D, false, false, OutOwn>(
-      blockIdx.x, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
-      p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
-      p.o_str, 0, s, s, scale, causal, nullptr, nullptr, 0, 0, oa);
-  const int kb2 = nkb - 1 - (int)blockIdx.x;
-  if (causal && paired && kb2 > (int)blockIdx.x) {
-    __syncthreads();
-    flash_bwd_dkv_block<D, false, false, OutOwn>(
-        kb2, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
-        p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
-        p.o_str, 0, s, s, scale, causal, nullptr, nullptr, 0, 0, oa);
-  }
-}
-
-#pragma clang diagnostic pop
-#endif  // GALV_FLASH_PACKED_TU
-
-// ---------------------------------------------------------------------------
-// packed documents on the packed-QKV buffer: the varlen work mapping (one
-// workgroup per (segment, head, 256-row block) of a cu_seqlens table) with
-// the packed-QKV addressing.  For segment i, head h, t0 = cu[i], bi = t0/s,
-// p0 = t0 - bi*s, g = h/qpg, slot = h%qpg, hq = G*qpg:
-//   row stride (q, k, v, dq)   b*G*(qpg+2)*D
-//   q / dq base                (((p0*b + bi)*G + g)*(qpg+2) + slot)*D
-//   k, v                       pointers pre-offset by qpg*D, (qpg+1)*D; group
-//                              base ((p0*b + bi)*G + g)*(qpg+2)*D
-//   o, dout, dk_exp, dv_exp    [s, b, hq, D]: base ((p0*b + bi)*hq + h)*D,
-//                              row stride b*hq*D
-//   lse, di                    [b, hq, s]: base (bi*hq + h)*s + p0
-// sbhd only, sq = skv = len, off = 0, no bias, no window.  As in the varlen
-// module there is no complementary pairing, blocks past the end of a short
-// segment leave before touching memory, a malformed entry is an empty
-// segment, and each body has one call site and is inlined into it.
-// Compiled through flash_attn_qkv_varlen.hip, for the reason given above
-// for the varlen and packed modules.
-// ---------------------------------------------------------------------------
-#ifdef GALV_FLASH_PACKED_VARLEN_TU
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wignored-attributes"
-#define PACKED_VARLEN_INLINE_CALL [[clang::always_inline]]
-
-struct PackedSeg {
-  int len;  // tokens in the segment (0 = nothing to do)
-  long q_base, kv_base, o_base, lse_base;
-  int qkv_str, o_str;
-};
-
-template <int D>
-DEV_INLINE PackedSeg packed_seg(const int* __restrict__ cu, int b, int s,
-                                int G, int qpg) {
-  PackedSeg p;
-  const int hq = G * qpg;
-  const int seg = blockIdx.y / hq;
-  const int h = blockIdx.y - seg * hq;
-  const int g = h / qpg;
-  const int slot = h - g * qpg;
-  const int t0 = cu[seg];
-  const int len = cu[seg + 1] - t0;
-  const int bi = t0 / s;
-  const int p0 = t0 - bi * s;
-  // a malformed table (negative offset, past the last row, straddling a
-  // row) maps to "empty" so no address is ever formed from it
-  const bool ok = t0 >= 0 && len > 0 && bi < b && p0 + len <= s;
-  p.len = ok ? len : 0;
-  const long row = (long)p0 * b + bi;
-  const long grp = (row * G + g) * (qpg + 2);
-  p.q_base = (grp + slot) * D;
-  p.kv_base = grp * D;
-  p.o_base = (row * hq + h) * D;
-  p.lse_base = ((long)bi * hq + h) * s + p0;
-  p.qkv_str = b * G * (qpg + 2) * D;
-  p.o_str = b * hq * D;
-  return p;
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_packed_varlen_fwd_kernel(const __bf16* __restrict__ qkv,
-                                    __bf16* __restrict__ o,
-                                    float* __restrict__ lse,
-                                    const int* __restrict__ cu, int b, int s,
-                                    int G, int qpg, float scale,
-                                    bool causal) {
-  constexpr int KB = 64, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_fwd_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
-  // workgroup-uniform, before any barrier; also covers len == 0
-  if ((int)blockIdx.x * QBF >= p.len) return;
-  const __bf16* k = qkv + (long)qpg * D;
-  const __bf16* v = k + D;
-  const OutOwn oa{p.o_base, p.o_str};
-  const float sl2e = scale * 1.4426950408889634f;
-  PACKED_VARLEN_INLINE_CALL flash_fwd_block<D, false, false, OutOwn>(
-      blockIdx.x, qkv, k, v, o, lse, smem, p.q_base, p.kv_base, p.lse_base,
-      p.qkv_str, p.qkv_str, 0, p.len, p.len, sl2e, causal, nullptr, 0, 0,
-      oa);
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_packed_varlen_bwd_dq_kernel(const __bf16* __restrict__ dout,
-                                       const __bf16* __restrict__ qkv,
-                                       const float* __restrict__ lse,
-                                       const float* __restrict__ di,
-                                       __bf16* __restrict__ dqkv,
-                                       const int* __restrict__ cu, int b,
-                                       int s, int G, int qpg, float scale,
-                                       bool causal) {
-  constexpr int KB = 32, QBF = 256;
-  constexpr int BUFSZ = 2 * KB * D;  // must match flash_bwd_dq_block
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
-  if ((int)blockIdx.x * QBF >= p.len) return;
-  const __bf16* k = qkv + (long)qpg * D;
-  const __bf16* v = k + D;
-  const OutOwn oa{p.o_base, p.o_str};
-  PACKED_VARLEN_INLINE_CALL flash_bwd_dq_block<D, false, false, OutOwn>(
-      blockIdx.x, dout, qkv, k, v, lse, di, dqkv, smem, p.q_base, p.kv_base,
-      p.lse_base, p.qkv_str, p.qkv_str, 0, p.len, p.len, scale, causal,
-      nullptr, 0, 0, oa);
-}
-
-template <int D>
-__global__ __launch_bounds__(512, 2)
-void flash_packed_varlen_bwd_dkv_kernel(const __bf16* __restrict__ dout,
-                                        const __bf16* __restrict__ qkv,
-                                        const float* __restrict__ lse,
-                                        const float* __restrict__ di,
-                                        __bf16* __restrict__ dk_exp,
-                                        __bf16* __restrict__ dv_exp,
-                                        const int* __restrict__ cu, int b,
-                                        int s, int G, int qpg, float scale,
-                                        bool causal) {
-  constexpr int QT = 64, KBW = 256;  // must match flash_bwd_dkv_phase
-  constexpr int BUFSZ = 2 * QT * D;
-  __shared__ __align__(16) __bf16 smem[2 * BUFSZ];
-  __shared__ __align__(16) float lsedi[4 * QT];
-  const PackedSeg p = packed_seg<D>(cu, b, s, G, qpg);
-  if ((int)blockIdx.x * KBW >= p.len) return;
-  const __bf16* k = qkv + (long)qpg * D;
-  const __bf16* v = k + D;
-  const OutOwn oa{p.o_base, p.o_str};
-  // the two phases of flash_bwd_dkv_block, dV then dK; dk_exp / dv_exp
-  // carry hq heads in o's layout
-  PACKED_VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, false, false, false,
-                                                OutOwn>(
-      blockIdx.x, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
-      p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
-      p.o_str, 0, p.len, p.len, scale, causal, nullptr, nullptr, 0, 0, oa);
-  __syncthreads();
-  PACKED_VARLEN_INLINE_CALL flash_bwd_dkv_phase<D, true, false, false,
-                                                OutOwn>(
-      blockIdx.x, dout, qkv, k, v, lse, di, dk_exp, dv_exp, smem, lsedi,
-      p.q_base, p.kv_base, p.o_base, p.lse_base, p.qkv_str, p.qkv_str,
-      p.o_str, 0, p.len, p.len, scale, causal, nullptr, nullptr, 0, 0, oa);
-}
-
-#pragma clang diagnostic pop
-#endif  // GALV_FLASH_PACKED_VARLEN_TU
-
-// ---------------------------------------------------------------------------
 // MFMA layout probe: one-wave 32x32x16 GEMM from global memory laid out by
 // the assumed fragment maps. Validated against torch matmul on-device.
 // ---------------------------------------------------------------------------
@@ -1574,98 +217,39 @@ __global__ void mfma_probe_kernel(const __bf16* __restrict__ A,  // [32][16]
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-#if !defined(GALV_FLASH_VARLEN_TU) && !defined(GALV_FLASH_PACKED_TU) && \
-    !defined(GALV_FLASH_PACKED_VARLEN_TU)
-template <int D>
-static void flash_fwd_launch_d(const __bf16* q, const __bf16* k,
-                               const __bf16* v, __bf16* o, float* lse, int b,
-                               int sq, int skv, int hq, int hkv, float scale,
-                               bool causal, const __bf16* bias,
-                               bool sbhd, int window, hipStream_t st) {
-  int nqb = (sq + 255) / 256;
-  // complementary-pair causal scheduling halves the grid; skip it when
-  // the halved grid underfills the 256-CU chip (small-seq shapes)
-  const bool paired = causal && ((nqb + 1) / 2) * (long)b * hq >= 256;
-  dim3 grid((causal && paired) ? (nqb + 1) / 2 : nqb, b * hq);
-  if (bias != nullptr)
-    hipLaunchKernelGGL((flash_fwd_kernel<D, true>), grid, dim3(512), 0, st,
-                       q, k, v, o, lse, b, sq, skv, hq, hkv, scale, causal,
-                       bias, paired, sbhd, window);
-  else if (window > 0)
-    hipLaunchKernelGGL((flash_fwd_kernel<D, false, true>), grid, dim3(512),
-                       0, st, q, k, v, o, lse, b, sq, skv, hq, hkv, scale,
-                       causal, nullptr, paired, sbhd, window);
-  else
-    hipLaunchKernelGGL((flash_fwd_kernel<D>), grid, dim3(512), 0, st, q, k,
-                       v, o, lse, b, sq, skv, hq, hkv, scale, causal,
-                       nullptr, paired, sbhd, 0);
-}
-
 void flash_fwd_launch(const __bf16* q, const __bf16* k, const __bf16* v,
                       __bf16* o, float* lse, int b, int sq, int skv, int hq,
                       int hkv, int d, float scale, bool causal,
                       hipStream_t st, const __bf16* bias, bool sbhd,
                       int window) {
-  if (d == 64)
-    flash_fwd_launch_d<64>(q, k, v, o, lse, b, sq, skv, hq, hkv, scale,
-                           causal, bias, sbhd, window, st);
-  else
-    flash_fwd_launch_d<128>(q, k, v, o, lse, b, sq, skv, hq, hkv, scale,
-                            causal, bias, sbhd, window, st);
+  with_head_dim(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    const int nqb = (sq + FwdTile<D>::QBF - 1) / FwdTile<D>::QBF;
+    const bool paired = flash_paired(nqb, b, hq, causal);
+    dim3 grid(paired ? (nqb + 1) / 2 : nqb, b * hq);
+    if (bias != nullptr)
+      hipLaunchKernelGGL((flash_fwd_kernel<D, true>), grid, dim3(512), 0, st,
+                         q, k, v, o, lse, b, sq, skv, hq, hkv, scale, causal,
+                         bias, paired, sbhd, window);
+    else if (window > 0)
+      hipLaunchKernelGGL((flash_fwd_kernel<D, false, true>), grid, dim3(512),
+                         0, st, q, k, v, o, lse, b, sq, skv, hq, hkv, scale,
+                         causal, nullptr, paired, sbhd, window);
+    else
+      hipLaunchKernelGGL((flash_fwd_kernel<D>), grid, dim3(512), 0, st, q, k,
+                         v, o, lse, b, sq, skv, hq, hkv, scale, causal,
+                         nullptr, paired, sbhd, 0);
+  });
 }
 
 void attn_di_launch(const __bf16* dout, const __bf16* o, float* di, int b,
-                    int sq, int hq, int d, hipStream_t st,
-                    bool sbhd = false) {
-  long rows = (long)b * sq * hq;
-  int grid = galv_grid((rows + 3) / 4);
-  if (d == 64)
-    hipLaunchKernelGGL((attn_di_kernel<64>), dim3(grid), dim3(256), 0, st,
-                       dout, o, di, b, sq, hq, sbhd);
-  else
-    hipLaunchKernelGGL((attn_di_kernel<128>), dim3(grid), dim3(256), 0, st,
-                       dout, o, di, b, sq, hq, sbhd);
-}
-
-template <int D>
-static void flash_bwd_launch_d(const __bf16* dout, const __bf16* q,
-                               const __bf16* k, const __bf16* v,
-                               const float* lse, const float* di, __bf16* dq,
-                               __bf16* dk_exp, __bf16* dv_exp, int b, int sq,
-                               int skv, int hq, int hkv, float scale,
-                               bool causal, const __bf16* bias, float* dbias,
-                               bool sbhd, int window, hipStream_t st) {
-  int nqb = (sq + 255) / 256;
-  const bool pq = causal && ((nqb + 1) / 2) * (long)b * hq >= 256;
-  dim3 gq((causal && pq) ? (nqb + 1) / 2 : nqb, b * hq);
-  int nkb = (skv + 255) / 256;
-  const bool pkv = causal && ((nkb + 1) / 2) * (long)b * hq >= 256;
-  dim3 gkv((causal && pkv) ? (nkb + 1) / 2 : nkb, b * hq);
-  if (bias != nullptr) {
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<D, true>), gq, dim3(512), 0, st,
-                       dout, q, k, v, lse, di, dq, b, sq, skv, hq, hkv,
-                       scale, causal, bias, pq, sbhd, window);
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<D, true>), gkv, dim3(512), 0,
-                       st, dout, q, k, v, lse, di, dk_exp, dv_exp, b, sq,
-                       skv, hq, hkv, scale, causal, bias, dbias, pkv, sbhd,
-                       window);
-  } else if (window > 0) {
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<D, false, true>), gq, dim3(512),
-                       0, st, dout, q, k, v, lse, di, dq, b, sq, skv, hq,
-                       hkv, scale, causal, nullptr, pq, sbhd, window);
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<D, false, true>), gkv,
-                       dim3(512), 0, st, dout, q, k, v, lse, di, dk_exp,
-                       dv_exp, b, sq, skv, hq, hkv, scale, causal, nullptr,
-                       nullptr, pkv, sbhd, window);
-  } else {
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<D>), gq, dim3(512), 0, st, dout,
-                       q, k, v, lse, di, dq, b, sq, skv, hq, hkv, scale,
-                       causal, nullptr, pq, sbhd, 0);
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<D>), gkv, dim3(512), 0, st,
-                       dout, q, k, v, lse, di, dk_exp, dv_exp, b, sq, skv,
-                       hq, hkv, scale, causal, nullptr, nullptr, pkv, sbhd,
-                       0);
-  }
+                    int sq, int hq, int d, hipStream_t st, bool sbhd) {
+  const long rows = (long)b * sq * hq;
+  const int grid = galv_grid((rows + 3) / 4);
+  with_head_dim(d, [&](auto dc) {
+    hipLaunchKernelGGL((attn_di_kernel<decltype(dc)::value>), dim3(grid),
+                       dim3(256), 0, st, dout, o, di, b, sq, hq, sbhd);
+  });
 }
 
 void flash_bwd_launch(const __bf16* dout, const __bf16* q, const __bf16* k,
@@ -1674,14 +258,41 @@ void flash_bwd_launch(const __bf16* dout, const __bf16* q, const __bf16* k,
                       int sq, int skv, int hq, int hkv, int d, float scale,
                       bool causal, hipStream_t st, const __bf16* bias,
                       float* dbias, bool sbhd, int window) {
-  if (d == 64)
-    flash_bwd_launch_d<64>(dout, q, k, v, lse, di, dq, dk_exp, dv_exp, b, sq,
-                           skv, hq, hkv, scale, causal, bias, dbias, sbhd,
-                           window, st);
-  else
-    flash_bwd_launch_d<128>(dout, q, k, v, lse, di, dq, dk_exp, dv_exp, b,
-                            sq, skv, hq, hkv, scale, causal, bias, dbias,
-                            sbhd, window, st);
+  with_head_dim(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    const int nqb = (sq + DqTile<D>::QBF - 1) / DqTile<D>::QBF;
+    const bool pq = flash_paired(nqb, b, hq, causal);
+    dim3 gq(pq ? (nqb + 1) / 2 : nqb, b * hq);
+    const int nkb = (skv + DkvTile<D>::KBW - 1) / DkvTile<D>::KBW;
+    const bool pkv = flash_paired(nkb, b, hq, causal);
+    dim3 gkv(pkv ? (nkb + 1) / 2 : nkb, b * hq);
+    if (bias != nullptr) {
+      hipLaunchKernelGGL((flash_bwd_dq_kernel<D, true>), gq, dim3(512), 0, st,
+                         dout, q, k, v, lse, di, dq, b, sq, skv, hq, hkv,
+                         scale, causal, bias, pq, sbhd, window);
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<D, true>), gkv, dim3(512), 0,
+                         st, dout, q, k, v, lse, di, dk_exp, dv_exp, b, sq,
+                         skv, hq, hkv, scale, causal, bias, dbias, pkv, sbhd,
+                         window);
+    } else if (window > 0) {
+      hipLaunchKernelGGL((flash_bwd_dq_kernel<D, false, true>), gq,
+                         dim3(512), 0, st, dout, q, k, v, lse, di, dq, b, sq,
+                         skv, hq, hkv, scale, causal, nullptr, pq, sbhd,
+                         window);
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<D, false, true>), gkv,
+                         dim3(512), 0, st, dout, q, k, v, lse, di, dk_exp,
+                         dv_exp, b, sq, skv, hq, hkv, scale, causal, nullptr,
+                         nullptr, pkv, sbhd, window);
+    } else {
+      hipLaunchKernelGGL((flash_bwd_dq_kernel<D>), gq, dim3(512), 0, st,
+                         dout, q, k, v, lse, di, dq, b, sq, skv, hq, hkv,
+                         scale, causal, nullptr, pq, sbhd, 0);
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<D>), gkv, dim3(512), 0, st,
+                         dout, q, k, v, lse, di, dk_exp, dv_exp, b, sq, skv,
+                         hq, hkv, scale, causal, nullptr, nullptr, pkv, sbhd,
+                         0);
+    }
+  });
 }
 
 void mfma_probe_launch(const __bf16* A, const __bf16* B, float* Dst, bool alt,
@@ -1693,189 +304,3 @@ void mfma_probe_launch(const __bf16* A, const __bf16* B, float* Dst, bool alt,
     hipLaunchKernelGGL((mfma_probe_kernel<false>), dim3(1), dim3(64), 0, st,
                        A, B, Dst);
 }
-
-#elif defined(GALV_FLASH_VARLEN_TU)
-
-// varlen: grid.x covers the longest segment, grid.y = (segment, head)
-template <int D>
-static void flash_varlen_fwd_launch_d(const __bf16* q, const __bf16* k,
-                                      const __bf16* v, __bf16* o, float* lse,
-                                      const int* cu, int nseg,
-                                      int max_seqlen, int b, int s, int hq,
-                                      int hkv, float scale, bool causal,
-                                      bool sbhd, hipStream_t st) {
-  dim3 grid((max_seqlen + 255) / 256, nseg * hq);
-  hipLaunchKernelGGL((flash_varlen_fwd_kernel<D>), grid, dim3(512), 0, st, q,
-                     k, v, o, lse, cu, b, s, hq, hkv, scale, causal, sbhd);
-}
-
-void flash_varlen_fwd_launch(const __bf16* q, const __bf16* k,
-                             const __bf16* v, __bf16* o, float* lse,
-                             const int* cu, int nseg, int max_seqlen, int b,
-                             int s, int hq, int hkv, int d, float scale,
-                             bool causal, bool sbhd, hipStream_t st) {
-  if (d == 64)
-    flash_varlen_fwd_launch_d<64>(q, k, v, o, lse, cu, nseg, max_seqlen, b,
-                                  s, hq, hkv, scale, causal, sbhd, st);
-  else
-    flash_varlen_fwd_launch_d<128>(q, k, v, o, lse, cu, nseg, max_seqlen, b,
-                                   s, hq, hkv, scale, causal, sbhd, st);
-}
-
-template <int D>
-static void flash_varlen_bwd_launch_d(const __bf16* dout, const __bf16* q,
-                                      const __bf16* k, const __bf16* v,
-                                      const float* lse, const float* di,
-                                      __bf16* dq, __bf16* dk_exp,
-                                      __bf16* dv_exp, const int* cu,
-                                      int nseg, int max_seqlen, int b, int s,
-                                      int hq, int hkv, float scale,
-                                      bool causal, bool sbhd,
-                                      hipStream_t st) {
-  dim3 grid((max_seqlen + 255) / 256, nseg * hq);
-  hipLaunchKernelGGL((flash_varlen_bwd_dq_kernel<D>), grid, dim3(512), 0, st,
-                     dout, q, k, v, lse, di, dq, cu, b, s, hq, hkv, scale,
-                     causal, sbhd);
-  hipLaunchKernelGGL((flash_varlen_bwd_dkv_kernel<D>), grid, dim3(512), 0,
-                     st, dout, q, k, v, lse, di, dk_exp, dv_exp, cu, b, s,
-                     hq, hkv, scale, causal, sbhd);
-}
-
-void flash_varlen_bwd_launch(const __bf16* dout, const __bf16* q,
-                             const __bf16* k, const __bf16* v,
-                             const float* lse, const float* di, __bf16* dq,
-                             __bf16* dk_exp, __bf16* dv_exp, const int* cu,
-                             int nseg, int max_seqlen, int b, int s, int hq,
-                             int hkv, int d, float scale, bool causal,
-                             bool sbhd, hipStream_t st) {
-  if (d == 64)
-    flash_varlen_bwd_launch_d<64>(dout, q, k, v, lse, di, dq, dk_exp, dv_exp,
-                                  cu, nseg, max_seqlen, b, s, hq, hkv, scale,
-                                  causal, sbhd, st);
-  else
-    flash_varlen_bwd_launch_d<128>(dout, q, k, v, lse, di, dq, dk_exp,
-                                   dv_exp, cu, nseg, max_seqlen, b, s, hq,
-                                   hkv, scale, causal, sbhd, st);
-}
-
-#elif defined(GALV_FLASH_PACKED_TU)
-
-// packed QKV: the dense grids (and their underfill-aware pairing rule) with
-// hq = G*qpg heads
-template <int D>
-static void flash_packed_fwd_launch_d(const __bf16* qkv, __bf16* o,
-                                      float* lse, int b, int s, int G,
-                                      int qpg, float scale, bool causal,
-                                      hipStream_t st) {
-  const int hq = G * qpg;
-  const int nqb = (s + 255) / 256;
-  const bool paired = causal && ((nqb + 1) / 2) * (long)b * hq >= 256;
-  dim3 grid(paired ? (nqb + 1) / 2 : nqb, b * hq);
-  hipLaunchKernelGGL((flash_packed_fwd_kernel<D>), grid, dim3(512), 0, st,
-                     qkv, o, lse, b, s, G, qpg, scale, causal, paired);
-}
-
-void flash_packed_fwd_launch(const __bf16* qkv, __bf16* o, float* lse, int b,
-                             int s, int G, int qpg, int d, float scale,
-                             bool causal, hipStream_t st) {
-  if (d == 64)
-    flash_packed_fwd_launch_d<64>(qkv, o, lse, b, s, G, qpg, scale, causal,
-                                  st);
-  else
-    flash_packed_fwd_launch_d<128>(qkv, o, lse, b, s, G, qpg, scale, causal,
-                                   st);
-}
-
-template <int D>
-static void flash_packed_bwd_launch_d(const __bf16* dout, const __bf16* qkv,
-                                      const float* lse, const float* di,
-                                      __bf16* dqkv, __bf16* dk_exp,
-                                      __bf16* dv_exp, int b, int s, int G,
-                                      int qpg, float scale, bool causal,
-                                      hipStream_t st) {
-  const int hq = G * qpg;
-  const int nb = (s + 255) / 256;  // q blocks == key blocks (sq == skv)
-  const bool paired = causal && ((nb + 1) / 2) * (long)b * hq >= 256;
-  dim3 grid(paired ? (nb + 1) / 2 : nb, b * hq);
-  hipLaunchKernelGGL((flash_packed_bwd_dq_kernel<D>), grid, dim3(512), 0, st,
-                     dout, qkv, lse, di, dqkv, b, s, G, qpg, scale, causal,
-                     paired);
-  hipLaunchKernelGGL((flash_packed_bwd_dkv_kernel<D>), grid, dim3(512), 0,
-                     st, dout, qkv, lse, di, dk_exp, dv_exp, b, s, G, qpg,
-                     scale, causal, paired);
-}
-
-void flash_packed_bwd_launch(const __bf16* dout, const __bf16* qkv,
-                             const float* lse, const float* di, __bf16* dqkv,
-                             __bf16* dk_exp, __bf16* dv_exp, int b, int s,
-                             int G, int qpg, int d, float scale, bool causal,
-                             hipStream_t st) {
-  if (d == 64)
-    flash_packed_bwd_launch_d<64>(dout, qkv, lse, di, dqkv, dk_exp, dv_exp,
-                                  b, s, G, qpg, scale, causal, st);
-  else
-    flash_packed_bwd_launch_d<128>(dout, qkv, lse, di, dqkv, dk_exp, dv_exp,
-                                   b, s, G, qpg, scale, causal, st);
-}
-
-#else  // GALV_FLASH_PACKED_VARLEN_TU
-
-// packed QKV + varlen: the varlen grid with hq = G*qpg heads
-template <int D>
-static void flash_packed_varlen_fwd_launch_d(const __bf16* qkv, __bf16* o,
-                                             float* lse, const int* cu,
-                                             int nseg, int max_seqlen, int b,
-                                             int s, int G, int qpg,
-                                             float scale, bool causal,
-                                             hipStream_t st) {
-  dim3 grid((max_seqlen + 255) / 256, nseg * G * qpg);
-  hipLaunchKernelGGL((flash_packed_varlen_fwd_kernel<D>), grid, dim3(512), 0,
-                     st, qkv, o, lse, cu, b, s, G, qpg, scale, causal);
-}
-
-void flash_packed_varlen_fwd_launch(const __bf16* qkv, __bf16* o, float* lse,
-                                    const int* cu, int nseg, int max_seqlen,
-                                    int b, int s, int G, int qpg, int d,
-                                    float scale, bool causal,
-                                    hipStream_t st) {
-  if (d == 64)
-    flash_packed_varlen_fwd_launch_d<64>(qkv, o, lse, cu, nseg, max_seqlen,
-                                         b, s, G, qpg, scale, causal, st);
-  else
-    flash_packed_varlen_fwd_launch_d<128>(qkv, o, lse, cu, nseg, max_seqlen,
-                                          b, s, G, qpg, scale, causal, st);
-}
-
-template <int D>
-static void flash_packed_varlen_bwd_launch_d(
-    const __bf16* dout, const __bf16* qkv, const float* lse, const float* di,
-    __bf16* dqkv, __bf16* dk_exp, __bf16* dv_exp, const int* cu, int nseg,
-    int max_seqlen, int b, int s, int G, int qpg, float scale, bool causal,
-    hipStream_t st) {
-  dim3 grid((max_seqlen + 255) / 256, nseg * G * qpg);
-  hipLaunchKernelGGL((flash_packed_varlen_bwd_dq_kernel<D>), grid, dim3(512),
-                     0, st, dout, qkv, lse, di, dqkv, cu, b, s, G, qpg,
-                     scale, causal);
-  hipLaunchKernelGGL((flash_packed_varlen_bwd_dkv_kernel<D>), grid,
-                     dim3(512), 0, st, dout, qkv, lse, di, dk_exp, dv_exp,
-                     cu, b, s, G, qpg, scale, causal);
-}
-
-void flash_packed_varlen_bwd_launch(const __bf16* dout, const __bf16* qkv,
-                                    const float* lse, const float* di,
-                                    __bf16* dqkv, __bf16* dk_exp,
-                                    __bf16* dv_exp, const int* cu, int nseg,
-                                    int max_seqlen, int b, int s, int G,
-                                    int qpg, int d, float scale, bool causal,
-                                    hipStream_t st) {
-  if (d == 64)
-    flash_packed_varlen_bwd_launch_d<64>(dout, qkv, lse, di, dqkv, dk_exp,
-                                         dv_exp, cu, nseg, max_seqlen, b, s,
-                                         G, qpg, scale, causal, st);
-  else
-    flash_packed_varlen_bwd_launch_d<128>(dout, qkv, lse, di, dqkv, dk_exp,
-                                          dv_exp, cu, nseg, max_seqlen, b, s,
-                                          G, qpg, scale, causal, st);
-}
-
-#endif  // TU selection

@@ -255,6 +255,19 @@ class _FlashAttentionVarlen(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None
 
 
+def _device_cu_seqlens(cu_seqlens, b, s, max_seqlen, like):
+    """A cu_seqlens table ready for the kernels: a CPU one is validated
+    against [b, s] and copied asynchronously to like's device; a device one
+    is trusted (the caller validated its host copy)."""
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
+        raise ValueError("cu_seqlens must be a 1-D int32 tensor")
+    if not cu_seqlens.is_cuda:
+        ref.check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
+        if like.is_cuda:
+            cu_seqlens = cu_seqlens.to(like.device, non_blocking=True)
+    return cu_seqlens.contiguous()
+
+
 def flash_attention_varlen(q, k, v, cu_seqlens, max_seqlen: int,
                            causal: bool = True,
                            softmax_scale: Optional[float] = None,
@@ -272,30 +285,28 @@ def flash_attention_varlen(q, k, v, cu_seqlens, max_seqlen: int,
     """
     b, s = (q.shape[1], q.shape[0]) if sbhd else (q.shape[0], q.shape[1])
     max_seqlen = int(max_seqlen)
-    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
-        raise ValueError("cu_seqlens must be a 1-D int32 tensor")
-    if not cu_seqlens.is_cuda:
-        ref.check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
-        if q.is_cuda:
-            cu_seqlens = cu_seqlens.to(q.device, non_blocking=True)
+    cu_seqlens = _device_cu_seqlens(cu_seqlens, b, s, max_seqlen, q)
     scale = softmax_scale if softmax_scale is not None \
         else 1.0 / math.sqrt(q.shape[-1])
     o, lse = _FlashAttentionVarlen.apply(
-        q.contiguous(), k.contiguous(), v.contiguous(),
-        cu_seqlens.contiguous(), max_seqlen, causal, scale, sbhd)
+        q.contiguous(), k.contiguous(), v.contiguous(), cu_seqlens,
+        max_seqlen, causal, scale, sbhd)
     return (o, lse) if return_lse else o
 
 
 class _FusedQKVAttention(torch.autograd.Function):
     """RoPE + flash attention on the packed linear_qkv output, native only.
     q, k and v are never separated in memory: RoPE rotates the q and k
-    slots in place, the packed flash kernels address the slots directly, and
-    one finishing kernel turns dqkv into the gradient of the packed buffer
-    (inverse rotation + GQA group sum).  ops/csrc/flash_attn.hip (packed
-    section), elementwise.hip (rope_qkv_kernel, qkv_grad_finish_kernel)."""
+    slots in place (tables [s, d/2], or per-row [s, b, d/2]), the packed
+    flash kernels address the slots directly, and one finishing kernel turns
+    dqkv into the gradient of the packed buffer (inverse rotation + GQA
+    group sum).  With cu_seqlens the flash_packed_varlen_* kernels
+    (ops/csrc/flash_attn_qkv_varlen.hip) run; cu None keeps the dense packed
+    kernels (flash_attn_qkv.hip) and their pairing.  elementwise.hip holds
+    rope_qkv_kernel and qkv_grad_finish_kernel."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, geom, causal, scale):
+    def forward(ctx, qkv, cos, sin, geom, cu, max_seqlen, causal, scale):
         ext = get_ext(False)
         # qkv is rewritten in place: tell autograd, so that a producer that
         # saved this buffer for its own backward fails loudly instead of
@@ -305,10 +316,15 @@ class _FusedQKVAttention(torch.autograd.Function):
         packed = qkv.view(*geom)
         if cos is not None:
             ext.rope_qkv_(packed, cos, sin)
-        o, lse = ext.flash_attn_qkv_fwd(packed, causal, scale)
+        if cu is None:
+            o, lse = ext.flash_attn_qkv_fwd(packed, causal, scale)
+        else:
+            o, lse = ext.flash_attn_qkv_varlen_fwd(packed, cu, max_seqlen,
+                                                   causal, scale)
         # the rotated buffer is what backward needs: nothing else is kept
-        ctx.save_for_backward(qkv, o, lse, cos, sin)
+        ctx.save_for_backward(qkv, o, lse, cos, sin, cu)
         ctx.geom = geom
+        ctx.max_seqlen = max_seqlen
         ctx.causal = causal
         ctx.scale = scale
         return o, qkv
@@ -316,14 +332,66 @@ class _FusedQKVAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do, _dbuf):
         if do is None:
-            return None, None, None, None, None, None
-        qkv, o, lse, cos, sin = ctx.saved_tensors
+            return (None,) * 8
+        qkv, o, lse, cos, sin, cu = ctx.saved_tensors
         ext = get_ext(False)
-        dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_bwd(
-            do.contiguous(), qkv.view(*ctx.geom), o, lse, ctx.causal,
-            ctx.scale)
+        if cu is None:
+            dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_bwd(
+                do.contiguous(), qkv.view(*ctx.geom), o, lse, ctx.causal,
+                ctx.scale)
+        else:
+            dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_varlen_bwd(
+                do.contiguous(), qkv.view(*ctx.geom), o, lse, cu,
+                ctx.max_seqlen, ctx.causal, ctx.scale)
         ext.qkv_grad_finish_(dqkv, dk_exp, dv_exp, cos, sin)
-        return dqkv.view(qkv.shape), None, None, None, None, None
+        return (dqkv.view(qkv.shape),) + (None,) * 7
+
+
+def _qkv_geom(qkv, num_groups, q_per_group, softmax_scale):
+    """-> the packed view [s, b, G, qpg+2, d] of qkv and the softmax scale."""
+    d = qkv.shape[2:].numel() // (num_groups * (q_per_group + 2))
+    scale = softmax_scale if softmax_scale is not None \
+        else 1.0 / math.sqrt(d)
+    return (qkv.shape[0], qkv.shape[1], num_groups, q_per_group + 2, d), scale
+
+
+def _fused_qkv_native(qkv, cos, sin, geom, cu_seqlens, max_seqlen, causal,
+                      scale):
+    if cos is not None:
+        cos = cos[:geom[0]].contiguous().float()
+        sin = sin[:geom[0]].contiguous().float()
+    # the buffer itself goes in, not a view of it: an in-place op on a view
+    # would make autograd copy the whole gradient back into the base
+    o, _ = _FusedQKVAttention.apply(qkv.contiguous(), cos, sin, geom,
+                                    cu_seqlens, max_seqlen, causal, scale)
+    return o
+
+
+def _rope_qk_rows(q, k, cos, sin):
+    """apply_rope on q and k with [s, d/2] or per-row [s, b, d/2] tables.
+    Per-row: the batch folds into the row axis, [s*b, 1, h, d] with a
+    [s*b, d/2] table, as runtime.transformer.rope.apply_rope_qk does."""
+    if cos.dim() == 3:
+        s, b = q.shape[0], q.shape[1]
+        cos, sin = cos.reshape(s * b, -1), sin.reshape(s * b, -1)
+        qf = apply_rope(q.reshape(s * b, 1, *q.shape[2:]), cos, sin)
+        kf = apply_rope(k.reshape(s * b, 1, *k.shape[2:]), cos, sin)
+        return qf.view(q.shape), kf.view(k.shape)
+    return apply_rope(q, cos, sin), apply_rope(k, cos, sin)
+
+
+def _split_qkv(qkv, geom, cos, sin):
+    """The composition the native path replaces: slice q, k and v out of
+    the packed buffer ([s, b, h, d] each, contiguous) and rotate q and k."""
+    s, b, _, slots, d = geom
+    qkv = qkv.view(*geom)
+    q = qkv[:, :, :, :slots - 2].reshape(s, b, -1, d)
+    k = qkv[:, :, :, slots - 2].reshape(s, b, -1, d)
+    v = qkv[:, :, :, slots - 1].reshape(s, b, -1, d)
+    q, k = q.contiguous(), k.contiguous()
+    if cos is not None:
+        q, k = _rope_qk_rows(q, k, cos, sin)
+    return q, k, v.contiguous()
 
 
 def fused_qkv_attention_native(qkv, d, cos, window=None) -> bool:
@@ -352,91 +420,16 @@ def fused_qkv_attention(qkv, cos, sin, num_groups: int, q_per_group: int,
     requires grad.  Everything else (CPU, fp32, other head dims, per-row
     tables, an effective sliding window) runs the composition of slice,
     apply_rope and flash_attention and leaves qkv alone."""
-    s, b = qkv.shape[0], qkv.shape[1]
-    d = qkv.shape[2:].numel() // (num_groups * (q_per_group + 2))
-    geom = (s, b, num_groups, q_per_group + 2, d)
-    scale = softmax_scale if softmax_scale is not None \
-        else 1.0 / math.sqrt(d)
-    if fused_qkv_attention_native(qkv, d, cos, window):
-        if cos is not None:
-            cos = cos[:s].contiguous().float()
-            sin = sin[:s].contiguous().float()
-        # the buffer itself goes in, not a view of it: an in-place op on a
-        # view would make autograd copy the whole gradient back into the base
-        o, _ = _FusedQKVAttention.apply(qkv.contiguous(), cos, sin, geom,
-                                        causal, scale)
-        return o
-    qkv = qkv.view(*geom)
-    q = qkv[:, :, :, :q_per_group].reshape(s, b, -1, d)
-    k = qkv[:, :, :, q_per_group].reshape(s, b, -1, d)
-    v = qkv[:, :, :, q_per_group + 1].reshape(s, b, -1, d)
-    q, k = q.contiguous(), k.contiguous()
-    if cos is not None:
-        if cos.dim() != 2:
-            raise ValueError("fused_qkv_attention: cos/sin must be [s, d/2]")
-        q, k = apply_rope(q, cos, sin), apply_rope(k, cos, sin)
-    return flash_attention(q, k, v.contiguous(), causal=causal,
+    geom, scale = _qkv_geom(qkv, num_groups, q_per_group, softmax_scale)
+    if fused_qkv_attention_native(qkv, geom[-1], cos, window):
+        return _fused_qkv_native(qkv, cos, sin, geom, None, None, causal,
+                                 scale)
+    if cos is not None and cos.dim() != 2:
+        raise ValueError("fused_qkv_attention: cos/sin must be [s, d/2]")
+    q, k, v = _split_qkv(qkv, geom, cos, sin)
+    return flash_attention(q, k, v, causal=causal,
                            softmax_scale=softmax_scale, window=window,
                            sbhd=True)
-
-
-class _FusedQKVAttentionVarlen(torch.autograd.Function):
-    """_FusedQKVAttention for packed documents: per-row RoPE tables
-    [s, b, d/2] (rank 3) as well as [s, d/2], and, with cu_seqlens, the
-    flash_packed_varlen_* kernels (ops/csrc/flash_attn.hip, packed varlen
-    section).  cu_seqlens None keeps the dense packed kernels and their
-    pairing.  Native only."""
-
-    @staticmethod
-    def forward(ctx, qkv, cos, sin, geom, cu, max_seqlen, causal, scale):
-        ext = get_ext(False)
-        # see _FusedQKVAttention.forward
-        ctx.mark_dirty(qkv)
-        ctx.set_materialize_grads(False)
-        packed = qkv.view(*geom)
-        if cos is not None:
-            ext.rope_qkv_(packed, cos, sin)
-        if cu is None:
-            o, lse = ext.flash_attn_qkv_fwd(packed, causal, scale)
-        else:
-            o, lse = ext.flash_attn_qkv_varlen_fwd(packed, cu, max_seqlen,
-                                                   causal, scale)
-        ctx.save_for_backward(qkv, o, lse, cos, sin, cu)
-        ctx.geom = geom
-        ctx.max_seqlen = max_seqlen
-        ctx.causal = causal
-        ctx.scale = scale
-        return o, qkv
-
-    @staticmethod
-    def backward(ctx, do, _dbuf):
-        if do is None:
-            return (None,) * 8
-        qkv, o, lse, cos, sin, cu = ctx.saved_tensors
-        ext = get_ext(False)
-        if cu is None:
-            dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_bwd(
-                do.contiguous(), qkv.view(*ctx.geom), o, lse, ctx.causal,
-                ctx.scale)
-        else:
-            dqkv, dk_exp, dv_exp = ext.flash_attn_qkv_varlen_bwd(
-                do.contiguous(), qkv.view(*ctx.geom), o, lse, cu,
-                ctx.max_seqlen, ctx.causal, ctx.scale)
-        ext.qkv_grad_finish_(dqkv, dk_exp, dv_exp, cos, sin)
-        return (dqkv.view(qkv.shape),) + (None,) * 7
-
-
-def _rope_qk_rows(q, k, cos, sin):
-    """apply_rope on q and k with [s, d/2] or per-row [s, b, d/2] tables.
-    Per-row: the batch folds into the row axis, [s*b, 1, h, d] with a
-    [s*b, d/2] table, as runtime.transformer.rope.apply_rope_qk does."""
-    if cos.dim() == 3:
-        s, b = q.shape[0], q.shape[1]
-        cos, sin = cos.reshape(s * b, -1), sin.reshape(s * b, -1)
-        qf = apply_rope(q.reshape(s * b, 1, *q.shape[2:]), cos, sin)
-        kf = apply_rope(k.reshape(s * b, 1, *k.shape[2:]), cos, sin)
-        return qf.view(q.shape), kf.view(k.shape)
-    return apply_rope(q, cos, sin), apply_rope(k, cos, sin)
 
 
 def fused_qkv_attention_varlen(qkv, cos, sin, num_groups: int,
@@ -458,11 +451,7 @@ def fused_qkv_attention_varlen(qkv, cos, sin, num_groups: int,
     as fused_qkv_attention does.  Everything else runs the composition of
     slice, apply_rope and flash_attention_varlen / flash_attention and
     leaves qkv alone."""
-    s, b = qkv.shape[0], qkv.shape[1]
-    d = qkv.shape[2:].numel() // (num_groups * (q_per_group + 2))
-    geom = (s, b, num_groups, q_per_group + 2, d)
-    scale = softmax_scale if softmax_scale is not None \
-        else 1.0 / math.sqrt(d)
+    geom, scale = _qkv_geom(qkv, num_groups, q_per_group, softmax_scale)
     if cos is not None and cos.dim() not in (2, 3):
         raise ValueError("fused_qkv_attention_varlen: cos/sin must be "
                          "[s, d/2] or [s, b, d/2]")
@@ -471,36 +460,19 @@ def fused_qkv_attention_varlen(qkv, cos, sin, num_groups: int,
             raise ValueError("fused_qkv_attention_varlen: cu_seqlens needs "
                              "max_seqlen")
         max_seqlen = int(max_seqlen)
-        if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
-            raise ValueError("cu_seqlens must be a 1-D int32 tensor")
-        if not cu_seqlens.is_cuda:
-            ref.check_cu_seqlens(cu_seqlens, b, s, max_seqlen)
-            if qkv.is_cuda:
-                cu_seqlens = cu_seqlens.to(qkv.device, non_blocking=True)
-        cu_seqlens = cu_seqlens.contiguous()
-    if use_native(qkv) and qkv.dtype == torch.bfloat16 and d in (64, 128):
-        if cos is not None:
-            cos = cos[:s].contiguous().float()
-            sin = sin[:s].contiguous().float()
-        # the buffer itself goes in, not a view of it (see
-        # fused_qkv_attention)
-        o, _ = _FusedQKVAttentionVarlen.apply(
-            qkv.contiguous(), cos, sin, geom, cu_seqlens, max_seqlen, causal,
-            scale)
-        return o
-    qkv = qkv.view(*geom)
-    q = qkv[:, :, :, :q_per_group].reshape(s, b, -1, d)
-    k = qkv[:, :, :, q_per_group].reshape(s, b, -1, d)
-    v = qkv[:, :, :, q_per_group + 1].reshape(s, b, -1, d)
-    q, k = q.contiguous(), k.contiguous()
-    if cos is not None:
-        q, k = _rope_qk_rows(q, k, cos, sin)
+        cu_seqlens = _device_cu_seqlens(cu_seqlens, geom[1], geom[0],
+                                        max_seqlen, qkv)
+    if use_native(qkv) and qkv.dtype == torch.bfloat16 \
+            and geom[-1] in (64, 128):
+        return _fused_qkv_native(qkv, cos, sin, geom, cu_seqlens, max_seqlen,
+                                 causal, scale)
+    q, k, v = _split_qkv(qkv, geom, cos, sin)
     if cu_seqlens is None:
-        return flash_attention(q, k, v.contiguous(), causal=causal,
+        return flash_attention(q, k, v, causal=causal,
                                softmax_scale=softmax_scale, sbhd=True)
-    return flash_attention_varlen(q, k, v.contiguous(), cu_seqlens,
-                                  max_seqlen, causal=causal,
-                                  softmax_scale=softmax_scale, sbhd=True)
+    return flash_attention_varlen(q, k, v, cu_seqlens, max_seqlen,
+                                  causal=causal, softmax_scale=softmax_scale,
+                                  sbhd=True)
 
 
 class _FlashBiasAttention(torch.autograd.Function):

@@ -22,12 +22,12 @@ def dev():
 
 
 class Spy:
-    """Counts _FusedQKVAttentionVarlen.forward calls while active."""
+    """Counts _FusedQKVAttention.forward calls while active."""
 
     def __enter__(self):
         from hetu_galvatron_amd.ops import functional
         self.calls = []
-        self.fn = functional._FusedQKVAttentionVarlen
+        self.fn = functional._FusedQKVAttention
         self.orig = orig = self.fn.forward
 
         def spy(ctx, *a):
