@@ -2,6 +2,12 @@
 // (or [s, b, h, D] with sbhd), bias, sliding window, cross lengths.  The
 // block bodies are in flash_attn_body.h; this module adds the dense
 // kernels, attn_di and the MFMA layout probe.
+//
+// The dense bodies are noinline and already spill; of the body header's
+// optional steps they keep only the rescale skip at D = 128.  The skip at
+// D = 64 and the mask split of dq each cost these kernels scratch.
+#define FLASH_SKIP_RESCALE(D) ((D) == 128)
+#define FLASH_DQ_MASK_SPLIT(D) 0
 #include "flash_attn_body.h"
 #include "flash_attn_launch.h"
 

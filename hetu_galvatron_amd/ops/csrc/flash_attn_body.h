@@ -70,13 +70,41 @@ struct DkvTile {
 
 DEV_INLINE float neg_big() { return -1e30f; }
 
+// Two of the forms that spare VALU work compute the same bits as the plain
+// ones but move registers about: skipping the forward's O rescale while no
+// running max of the wave moves, and a wave-uniform branch around a masked
+// and an unmasked element loop in dq.  A module whose bodies of a
+// head dimension D they would cost scratch or occupancy defines the step to
+// 0 for that D before it includes this header and keeps the plain form
+// (docs/KERNELS.md, "Softmax VALU work").
+#ifndef FLASH_SKIP_RESCALE
+#define FLASH_SKIP_RESCALE(D) 1
+#endif
+#ifndef FLASH_DQ_MASK_SPLIT
+#define FLASH_DQ_MASK_SPLIT(D) 1
+#endif
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+
+// (lo, hi) rounded to bf16 in one word: the vector conversion is a single
+// v_cvt_pk_bf16_f32, the rounding of two scalar conversions.
 DEV_INLINE unsigned pack_bf16(float lo, float hi) {
-  union { __hip_bfloat162 h2; unsigned u; } cv;
-  cv.h2 = __hip_bfloat162(__float2bfloat16(lo), __float2bfloat16(hi));
+  union { bf16x2 h2; unsigned u; } cv;
+  cv.h2 = __builtin_convertvector(f32x2{lo, hi}, bf16x2);
   return cv.u;
 }
 
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+// Combine x of lane l with x of lane l ^ 32 without LDS: permlane32_swap of
+// x with itself leaves the lower half's x in every lane of the first word
+// and the upper half's in the second.  Both lanes of a pair combine the same
+// two values, in either order: use with commutative operations only.
+DEV_INLINE void both_halves(float x, float& lower, float& upper) {
+  const unsigned u = __float_as_uint(x);
+  auto r2 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  lower = __uint_as_float(r2[0]);
+  upper = __uint_as_float(r2[1]);
+}
 
 // 16 bias values for one 32-key D-layout column: row(r) = 8*(r>>2) +
 // 4*hi + (r&3) — each r-quad is 4 contiguous bf16, so 4 8-byte loads
@@ -465,23 +493,42 @@ void flash_fwd_block(int qblk, const __bf16* __restrict__ q,
       float mt = pv[0];
 #pragma unroll
       for (int i = 1; i < 32; ++i) mt = fmaxf(mt, pv[i]);
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+      float m_lo, m_hi;
+      both_halves(mt, m_lo, m_hi);
+      mt = fmaxf(m_lo, m_hi);
       const float mn = fmaxf(m_run, mt);
-      const float alpha = (m_run <= neg_big()) ? 0.f : exp2f(m_run - mn);
-      const bool dead = (mn <= neg_big());
+      // exp2 here is the bare v_exp_f32.  exp2f() wraps it for results in
+      // the denormal range: for an argument >= -126 the wrapper adds 0 and
+      // scales by 2^0, i.e. returns this instruction's result; below -126
+      // it returns a denormal where the instruction returns 0.  Such a P or
+      // alpha is at most 2^-126 beside a row sum >= 1 (the row's maximum
+      // contributes exp2(0)), so it cannot move an fp32 accumulator.
+      const float alpha = (m_run <= neg_big())
+                              ? 0.f : __builtin_amdgcn_exp2f(m_run - mn);
+      // A row is dead while every key seen so far is masked: mn and all of
+      // pv are neg_big().  Subtracting 0 there gives exp2(neg_big()) = 0
+      // exactly; one select per tile, not one per element.
+      const float msub = (mn <= neg_big()) ? 0.f : mn;
       float ps = 0.f;
 #pragma unroll
       for (int i = 0; i < 32; ++i) {
-        pv[i] = dead ? 0.f : exp2f(pv[i] - mn);
+        pv[i] = __builtin_amdgcn_exp2f(pv[i] - msub);
         ps += pv[i];
       }
-      ps += __shfl_xor(ps, 32, 64);
+      float ps_lo, ps_hi;
+      both_halves(ps, ps_lo, ps_hi);
+      ps = ps_lo + ps_hi;
       l_run = l_run * alpha + ps;
       m_run = mn;
+      // alpha == 1 in every lane (no running max of the wave moved): the
+      // rescale would multiply by one.  The ballot is wave-uniform.
+      if (!FLASH_SKIP_RESCALE(D) ||
+          __builtin_amdgcn_ballot_w64(alpha != 1.f) != 0) {
 #pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
+        for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
+          for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
+      }
 
       // ---- P -> bf16 PV fragments via cvt_pk + permlane32_swap ----
       // frag[ks] holds P[q=lane][16*ks + 8*hi + j], j=0..7, as 4 u32 words
@@ -673,26 +720,42 @@ void flash_bwd_dq_block(int qblk, const __bf16* __restrict__ dout,
       const __bf16* brow = nullptr;
       if (BIASED)
         brow = bias + bias_base + (long)min(qg, sq - 1) * skv;
-      const bool need_mask =
+      // The test is the same in every lane of the wave, but q0w comes from
+      // the thread index and a noinline body gets its arguments in vector
+      // registers: read it from the first lane, so that it is a scalar
+      // branch around two plain loops and not an exec-masked region per
+      // element.
+      constexpr bool SPLIT = FLASH_DQ_MASK_SPLIT(D);
+      bool need_mask =
           (causal && kv0 + KB > q0w + off + 1) || (kv0 + KB > skv) ||
           (WINDOWED && kv0 < q0w + 32 + off - window + 1);
+      if (SPLIT) need_mask = __builtin_amdgcn_readfirstlane(need_mask);
       float dsv[16];
       float bv[16];
       if (BIASED)
         load_bias16(brow, kv0 + 4 * hi, skv, bv);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
+      auto element = [&](int r, bool masked) {
         float sc = st[r] * sl2e;
         if (BIASED) sc += bv[r];
         const float e = __expf(sc - lse_c);
         float pr = e;
-        if (need_mask) {
+        if (masked) {
           const int key = kv0 + mfma32_d_row(lane, r);
           const bool ok = key < skv && !(causal && key > qg + off) &&
                           !(WINDOWED && key <= qg + off - window);
           pr = ok ? e : 0.f;
         }
         dsv[r] = pr * (dp[r] - di_c) * scale;
+      };
+      if (!SPLIT) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) element(r, need_mask);
+      } else if (need_mask) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) element(r, true);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) element(r, false);
       }
 
       // pack dS^T to MFMA B-fragments (cvt_pk + permlane32_swap)

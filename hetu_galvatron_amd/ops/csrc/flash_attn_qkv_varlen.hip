@@ -5,6 +5,10 @@
 // the varlen module there is no complementary pairing, blocks past the end
 // of a short segment leave before touching memory, a malformed entry is an
 // empty segment, and each body has one call site and is inlined into it.
+//
+// The dq mask split raises the D = 64 dq kernel past 128 VGPRs, i.e. from
+// two resident workgroups per CU to one; it is left out at that D.
+#define FLASH_DQ_MASK_SPLIT(D) ((D) == 128)
 #include "flash_attn_body.h"
 #include "flash_attn_launch.h"
 

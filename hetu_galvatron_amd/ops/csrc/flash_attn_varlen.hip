@@ -9,6 +9,10 @@
 //
 // Each body has one call site here and is inlined into it (off = 0 and
 // sq == skv fold away; no scratch at D=64).
+//
+// The dq mask split raises the D = 64 dq kernel past 128 VGPRs, i.e. from
+// two resident workgroups per CU to one; it is left out at that D.
+#define FLASH_DQ_MASK_SPLIT(D) ((D) == 128)
 #include "flash_attn_body.h"
 #include "flash_attn_launch.h"
 
