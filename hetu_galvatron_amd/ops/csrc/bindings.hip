@@ -752,19 +752,61 @@ void qkv_grad_finish_(Tensor dqkv, const Tensor& dk_exp, const Tensor& dv_exp,
                          (int)dqkv.size(4), cur_stream());
 }
 
+// What the two decode bindings share: q [b,hq,d], k_cache / v_cache
+// [b,max_s,hkv,d], all bf16, contiguous, on q's device.
+struct DecodeDims {
+  int b, hq, hkv, d, max_s;
+};
+
+DecodeDims decode_dims(const Tensor& q, const Tensor& k_cache,
+                       const Tensor& v_cache, const char* who) {
+  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
+              who, ": q must be bf16 [b,hq,d], contiguous on GPU, got ",
+              q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
+  TORCH_CHECK(k_cache.is_cuda() && k_cache.device() == q.device() &&
+                  k_cache.is_contiguous(), who,
+              ": k_cache must be contiguous on q's GPU, got ",
+              k_cache.device(), " ", k_cache.sizes(), " strides ",
+              k_cache.strides());
+  TORCH_CHECK(is_bf16(k_cache) && k_cache.dim() == 4 &&
+                  k_cache.size(0) == q.size(0) &&
+                  k_cache.size(3) == q.size(2), who,
+              ": k_cache must be bf16 [b,max_s,hkv,d] with q's batch and "
+              "head dim, got ", k_cache.scalar_type(), " ", k_cache.sizes(),
+              " for q ", q.sizes());
+  TORCH_CHECK(v_cache.is_cuda() && v_cache.device() == q.device() &&
+                  v_cache.is_contiguous(), who,
+              ": v_cache must be contiguous on q's GPU, got ",
+              v_cache.device(), " ", v_cache.sizes(), " strides ",
+              v_cache.strides());
+  TORCH_CHECK(is_bf16(v_cache) && v_cache.sizes() == k_cache.sizes(), who,
+              ": v_cache must be bf16 and shaped like k_cache, got ",
+              v_cache.scalar_type(), " ", v_cache.sizes(), " for k_cache ",
+              k_cache.sizes());
+  DecodeDims g;
+  g.b = q.size(0); g.hq = q.size(1); g.d = q.size(2);
+  g.max_s = k_cache.size(1); g.hkv = k_cache.size(2);
+  TORCH_CHECK(g.d == 64 || g.d == 128, who,
+              ": head dim must be 64|128, got q ", q.sizes());
+  TORCH_CHECK(g.b > 0 && g.hq > 0 && g.hkv > 0 && g.hq % g.hkv == 0, who,
+              ": GQA needs hq % hkv == 0, got hq ", g.hq, " (q ", q.sizes(),
+              ") and hkv ", g.hkv, " (k_cache ", k_cache.sizes(), ")");
+  return g;
+}
+
 // Single-token decode attention against a KV cache (serving path).
 // q: [b,hq,d]; k_cache/v_cache: [b,max_s,hkv,d]; attends to [0, cur_len).
 Tensor decode_attn(const Tensor& q, const Tensor& k_cache,
                    const Tensor& v_cache, int64_t cur_len, double scale,
                    int64_t start = 0) {
-  CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
-  TORCH_CHECK(is_bf16(q), "decode_attn: bf16 only");
-  TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4, "decode_attn shapes");
-  const int b = q.size(0), hq = q.size(1), d = q.size(2);
-  const int max_s = k_cache.size(1), hkv = k_cache.size(2);
-  TORCH_CHECK(d == 64 || d == 128, "decode_attn: head dim must be 64|128");
-  TORCH_CHECK(cur_len >= 1 && cur_len <= max_s, "decode_attn: bad cur_len");
-  TORCH_CHECK(start >= 0 && start < cur_len, "decode_attn: bad start");
+  const DecodeDims g = decode_dims(q, k_cache, v_cache, "decode_attn");
+  const int b = g.b, hq = g.hq, d = g.d, max_s = g.max_s, hkv = g.hkv;
+  TORCH_CHECK(cur_len >= 1 && cur_len <= max_s,
+              "decode_attn: cur_len must be in [1, max_s], got ", cur_len,
+              " for k_cache ", k_cache.sizes());
+  TORCH_CHECK(start >= 0 && start < cur_len,
+              "decode_attn: start must be in [0, cur_len), got ", start,
+              " for cur_len ", cur_len);
   // windowed decode (mistral): positions [start, cur_len).  The kernels
   // are unchanged — advancing the cache pointers by start rows shifts
   // every (b, h) address uniformly within its batch row.
@@ -797,13 +839,17 @@ Tensor decode_attn(const Tensor& q, const Tensor& k_cache,
 Tensor decode_attn_graph(const Tensor& q, const Tensor& k_cache,
                          const Tensor& v_cache, const Tensor& cur_len_dev,
                          int64_t max_len, double scale) {
-  CHECK_GPU(q); CHECK_GPU(cur_len_dev);
-  TORCH_CHECK(is_bf16(q) && q.dim() == 3, "decode_attn_graph: bf16 [b,hq,d]");
-  TORCH_CHECK(cur_len_dev.scalar_type() == at::kInt, "cur_len_dev: int32");
-  const int b = q.size(0), hq = q.size(1), d = q.size(2);
-  const int max_s = k_cache.size(1), hkv = k_cache.size(2);
-  TORCH_CHECK(d == 64 || d == 128, "decode_attn_graph: head dim 64|128");
-  TORCH_CHECK(max_len >= 1 && max_len <= max_s, "bad max_len");
+  const DecodeDims g = decode_dims(q, k_cache, v_cache, "decode_attn_graph");
+  const int b = g.b, hq = g.hq, d = g.d, max_s = g.max_s, hkv = g.hkv;
+  TORCH_CHECK(cur_len_dev.is_cuda() && cur_len_dev.device() == q.device() &&
+                  cur_len_dev.scalar_type() == at::kInt &&
+                  cur_len_dev.numel() == 1,
+              "decode_attn_graph: cur_len_dev must be one int32 on q's GPU, "
+              "got ", cur_len_dev.scalar_type(), " ", cur_len_dev.sizes(),
+              " on ", cur_len_dev.device());
+  TORCH_CHECK(max_len >= 1 && max_len <= max_s,
+              "decode_attn_graph: max_len must be in [1, max_s], got ",
+              max_len, " for k_cache ", k_cache.sizes());
   auto o = at::empty_like(q);
   int n_chunks = b * hq >= 256 ? 1 : std::max(1, 512 / (b * hq));
   n_chunks = std::min<int>(n_chunks, (int)((max_len + 127) / 128));

@@ -411,7 +411,10 @@ __global__ void decode_attn_split_kernel(
   extern __shared__ __align__(16) float wsm[];  // [chunk] weights
   __shared__ float red[2][8];
   if (cur_len_dev != nullptr) {
-    cur_len = *cur_len_dev;
+    // the launch (grid, LDS, the caller's max_len <= max_s check) is sized
+    // for the cur_len passed by value: a larger device value must not read
+    // past it
+    cur_len = min(*cur_len_dev, cur_len);
     chunk = (cur_len + gridDim.y - 1) / gridDim.y;
   }
   const int bh = blockIdx.x;

@@ -2,8 +2,8 @@
 
 A plain helper module (not a conftest): `test_kernel_oracle.py` checks on the
 CPU that the rules below accept the fp32 `reference_ops` and reject planted
-mutants; `test_gpu_kernel_edges.py` applies the same rules, on the same
-inputs, to the HIP kernels.
+mutants; `test_gpu_kernel_edges.py` and `test_gpu_decode_sumsq.py` apply the
+same rules, on the same inputs, to the HIP kernels.
 
 Oracles
 -------
@@ -20,7 +20,7 @@ Comparison rules
    run alone in a small call.  No tolerance.
 
 2. fp32 accumulations (`assert_accum`; dw, db, sumexp, dprobs, scatter-adds,
-   grouped dW, the fp32 optimizer state).  With E_ref = max|ref32 - oracle|,
+   grouped dW, the fp32 optimizer state, the grad-norm sum of squares).  With E_ref = max|ref32 - oracle|,
    the error of the fp32 `reference_ops` result on the same inputs,
 
        max|got - oracle|  <=  ACCUM_MULT * max(E_ref, 2^-24 * max|oracle|)
@@ -53,6 +53,12 @@ Comparison rules
      ce dlogits      |gout| * (p * (1 + |logit - max|) + onehot)
      unpermute, grouped GEMM fwd / dA
                      the same product with every operand's absolute value
+     decode o        sum_p w_p (|v_pd| + |o_d|)
+                           * (1 + |s_p - m| + scale_qk sum_i |q_i k_pi|)
+                     (the same product with absolute values, each weight
+                     times the factor by which __expf's argument rounding
+                     and the fp32 score's own rounding grow it; |o_d| is
+                     the normaliser's share)
 
    adamw `out` is not under this rule: it is the cast of the kernel's own
    new master and must `torch.equal` that master cast to the out dtype.
@@ -295,6 +301,77 @@ def grouped_gemm_bwd(dc, a, w, counts):
         dw[e] = a[s:s + m].T @ dc[s:s + m]
         s += m
     return da, dw
+
+
+def _decode_window(q, kc, vc, cur, start):
+    """q as [b, hkv, rep, d]; k, v of the window as [b, hkv, n, d]."""
+    q, kc, vc = f64(q), f64(kc), f64(vc)
+    b, hq, d = q.shape
+    hkv = kc.shape[2]
+    assert hq % hkv == 0 and 0 <= start < cur <= kc.shape[1]
+    k = kc[:, start:cur].permute(0, 2, 1, 3)
+    v = vc[:, start:cur].permute(0, 2, 1, 3)
+    return q.reshape(b, hkv, hq // hkv, d), k, v
+
+
+def decode_attn(q, kc, vc, cur, scale, start=0):
+    """o[b, h] = sum_p softmax_p(scale * q[b, h] . k[b, p, h // rep]) *
+    v[b, p, h // rep] over the positions p in [start, cur).  q [b, hq, d],
+    caches [b, max_s, hkv, d].  -> o [b, hq, d] and the scores s, their
+    max m and the weights w per (b, h) (s, w: [b, hq, n]; m: [b, hq])."""
+    qg, k, v = _decode_window(q, kc, vc, cur, start)
+    b, hkv, rep, d = qg.shape
+    s = (qg @ k.transpose(-1, -2)) * scale            # [b, hkv, rep, n]
+    m = s.amax(-1, keepdim=True)
+    e = torch.exp(s - m)
+    w = e / e.sum(-1, keepdim=True)
+    o = (w @ v).reshape(b, hkv * rep, d)
+    n = s.shape[-1]
+    return o, dict(s=s.reshape(b, -1, n), m=m.reshape(b, -1),
+                   w=w.reshape(b, -1, n))
+
+
+def decode_scale(q, kc, vc, cur, scale, start=0, o=None, aux=None):
+    """Rule-3 scale of decode o (docstring table)."""
+    if aux is None:
+        o, aux = decode_attn(q, kc, vc, cur, scale, start)
+    qg, k, v = _decode_window(q, kc, vc, cur, start)
+    b, hkv, rep, d = qg.shape
+    s, m, w = (aux[n].reshape(b, hkv, rep, -1) for n in ("s", "m", "w"))
+    amp = 1 + (s - m).abs() + scale * (qg.abs() @ k.abs().transpose(-1, -2))
+    wa = w * amp
+    sc = wa @ v.abs() + f64(o).reshape(b, hkv, rep, d).abs() \
+        * wa.sum(-1, keepdim=True)
+    return sc.reshape(b, hkv * rep, d)
+
+
+def decode_chunks(b, hq, n, max_len=None):
+    """-> (n_chunks, chunk) of a window of n positions: the chunk count as
+    `decode_attn` in ops/csrc/bindings.hip forms it (fill 512 workgroups
+    when b*hq < 256, chunks of at least 128 positions, at most 8192 for the
+    LDS weight buffer) and chunk = ceil(n / n_chunks).  n_chunks == 1 is the
+    single-block kernel.  With max_len (`decode_attn_graph`) the count comes
+    from max_len and the split kernel sizes the chunk on the device from the
+    current n, which can leave empty tail chunks."""
+    m = n if max_len is None else max_len
+    nc = 1 if b * hq >= 256 else max(1, 512 // (b * hq))
+    nc = min(nc, (m + 127) // 128)
+    nc = max(nc, (m + 8191) // 8192)
+    return nc, -(-n // nc)
+
+
+def sumsq(xs):
+    """Sum of squares over a list of tensors, fp64 [1]."""
+    return sum((f64(x) ** 2).sum() for x in xs).reshape(1) if xs \
+        else torch.zeros(1, dtype=torch.float64)
+
+
+def sumsq_ref32(xs):
+    """What `grad_sumsq_owned` computes per block, added up in fp32."""
+    tot = torch.zeros((), dtype=torch.float32)
+    for x in xs:
+        tot = tot + (x.float() * x.float()).sum()
+    return tot.reshape(1)
 
 
 # ---------------------------------------------------------------------------
@@ -616,3 +693,207 @@ def gg_inputs(counts, K, N, seed=0):
     w = (torch.randn(E, K, N, generator=g) / 8 - 0.01).bfloat16()
     dc = (torch.randn(M, N, generator=g) + 0.05).bfloat16()
     return a, w, dc
+
+
+# ---- decode attention ------------------------------------------------------
+# (b, hq, hkv, max_s, n): n is the attended window cur - start, which is what
+# selects the kernel path; cur = start + n.  Every case runs at both
+# DECODE_DIMS, and the decode_attn ones at both DECODE_STARTS (37 is no
+# multiple of any chunk below).
+DECODE_DIMS = [64, 128]
+DECODE_STARTS = [0, 37]
+DECODE_SINGLE = [(8, 32, 2, 512, n) for n in (1, 2, 255, 256, 257, 300)]
+DECODE_SPLIT = [(1, 4, 2, 1280, 128),       # one chunk: the single-block path
+                (1, 4, 2, 1280, 129),       # 2 chunks, 65 + 64
+                (1, 4, 2, 1280, 257),       # 3 chunks, 86 + 86 + 85
+                (1, 4, 2, 1280, 1025),      # 9 chunks, 8 x 114 + 113
+                (1, 8, 1, 1280, 257)]       # GQA ratio 8
+DECODE_LDS = [(8, 32, 1, 8320, 8192),       # single block, 32 KiB of weights
+              (8, 32, 1, 8320, 8193)]       # the cap: 2 chunks, 4097 + 4096
+DECODE_GRAPH = [(1, 4, 2, 2048, n) for n in (1, 17, 2047, 2048)]
+DECODE_GRAPH_MAX_LEN = 2048                 # 16 chunks, sized on the device
+
+
+def decode_needles(b, hq, d, n, max_len=None):
+    """Window-relative needle positions: the window's ends, both sides of
+    every chunk boundary, the 256-thread stripe and the PSL = 256/(d/8)
+    V slices."""
+    nc, chunk = decode_chunks(b, hq, n, max_len)
+    psl = 256 // (d // 8)
+    pos = {0, 1, n - 2, n - 1, 255, 256, 257, psl - 1, psl, psl + 1}
+    for j in range(1, nc):
+        pos |= {j * chunk - 1, j * chunk}
+    return sorted(p for p in pos if 0 <= p < n)
+
+
+def decode_inputs(b, hq, hkv, d, max_s, cur, start=0, seed=0, max_len=None):
+    """q [b, hq, d], kc, vc [b, max_s, hkv, d] in bf16 with a peaked softmax.
+    The heads of a kv group share a direction (q = dir + 0.5 noise), and
+    at every needle position the key is that group's mean q direction, scaled
+    to a score of ln(n) + 1.5 +- 0.75 (a different one per needle, so that
+    chunk maxima differ), with a V row of +-[1, 3).  Needles then carry a few
+    per cent to tens of per cent of the weight each; the rest is randn.
+    Decoys (stronger needles) sit on the two rows before `start` and after
+    `cur`, where a kernel that read them would show; the GPU tests overwrite
+    everything outside [start, cur) with NaN."""
+    g = _gen(9000 + seed)
+    rep, n, scale = hq // hkv, cur - start, d ** -0.5
+    gdir = torch.randn(b, hkv, 1, d, generator=g)
+    q = gdir + 0.5 * torch.randn(b, hkv, rep, d, generator=g)
+    q = q.reshape(b, hq, d).bfloat16()
+    kc = torch.randn(b, max_s, hkv, d, generator=g).bfloat16()
+    vc = torch.randn(b, max_s, hkv, d, generator=g).bfloat16()
+    qg = q.float().reshape(b, hkv, rep, d)
+    u = qg.mean(2)
+    u = u / u.norm(dim=-1, keepdim=True)                    # [b, hkv, d]
+    align = (qg * u[:, :, None]).sum(-1).mean(-1)           # mean q . u
+    rel = decode_needles(b, hq, d, n, max_len)
+    decoy = [r for r in (-2, -1, n, n + 1) if 0 <= start + r < max_s]
+    pos = torch.tensor([start + r for r in rel + decoy])
+    t = math.log(n) + 1.5 + (torch.rand(len(pos), generator=g) - 0.5) * 1.5
+    t[len(rel):] += 1.0
+    gain = t[None, :, None] / (scale * align)[:, None, :]   # [b, P, hkv]
+    kc[:, pos] = (gain[..., None] * u[:, None]).bfloat16()
+    mag = 1 + 2 * torch.rand(b, len(pos), hkv, d, generator=g)
+    sign = torch.randint(0, 2, mag.shape, generator=g) * 2 - 1
+    vc[:, pos] = (mag * sign).bfloat16()
+    return q, kc, vc
+
+
+def decode_extreme_inputs(b, hq, hkv, d, max_s, cur, seed=0):
+    """Scores spanning +-60 in every head but head 0, whose scores are all
+    below -100: every key carries 6 * e (e the unit diagonal), q of head 0
+    is -50 / scale * e, and the other heads' q are scaled to a score range
+    of 120 and centred with their own component along e."""
+    g = _gen(9500 + seed)
+    scale = d ** -0.5
+    e = torch.full((d,), d ** -0.5)
+    kc = (torch.randn(b, max_s, hkv, d, generator=g) + 6 * e).bfloat16()
+    vc = (torch.randn(b, max_s, hkv, d, generator=g) + 0.3).bfloat16()
+    q = torch.randn(b, hq, d, generator=g)
+    q = q - (q @ e)[..., None] * e           # no common offset: both signs
+    s = decode_attn(q, kc, vc, cur, scale)[1]["s"]
+    hi, lo = s.amax(-1, keepdim=True), s.amin(-1, keepdim=True)
+    f = 120.0 / (hi - lo)
+    q = (q * f - f * (hi + lo) / 2 / (scale * 6) * e).float()
+    q[:, 0] = -50.0 / scale * e
+    return q.bfloat16(), kc, vc
+
+
+class DecodeCase:
+    """Inputs of one decode case with their oracle and rule-3 scale."""
+
+    def __init__(self, b, hq, hkv, d, max_s, n, start=0, max_len=None,
+                 extreme=False):
+        self.b, self.hq, self.hkv, self.d, self.max_s = b, hq, hkv, d, max_s
+        self.n, self.start, self.cur = n, start, start + n
+        self.max_len, self.scale = max_len, d ** -0.5
+        self.nc, self.chunk = decode_chunks(b, hq, n, max_len)
+        if extreme:
+            self.q, self.kc, self.vc = decode_extreme_inputs(
+                b, hq, hkv, d, max_s, self.cur)
+        else:
+            self.q, self.kc, self.vc = decode_inputs(
+                b, hq, hkv, d, max_s, self.cur, start, 0, max_len)
+        self.o, self.aux = decode_attn(self.q, self.kc, self.vc, self.cur,
+                                       self.scale, start)
+        self.sc = decode_scale(self.q, self.kc, self.vc, self.cur, self.scale,
+                               start, self.o, self.aux)
+        self.tag = (f"b={b} hq={hq} hkv={hkv} d={d} n={n} start={start}"
+                    f" chunks={self.nc}x{self.chunk}")
+
+    def ref32(self):
+        """The CPU branch of ops.decode_attention (fp32), bf16 out."""
+        from hetu_galvatron_amd.ops import decode_attention
+        kc, vc = self.kc, self.vc
+        if self.start:
+            # the op takes a window counted back from cur_len
+            return decode_attention(self.q, kc, vc, self.cur, self.scale,
+                                    window=self.n)
+        return decode_attention(self.q, kc, vc, self.cur, self.scale)
+
+
+_DECODE_CASES = {}
+
+
+def decode_case(*key, **kw):
+    """DecodeCase(*key), built once and shared between tests (read only)."""
+    k = key + tuple(sorted(kw.items()))
+    if k not in _DECODE_CASES:
+        if len(_DECODE_CASES) >= 4:          # the LDS cases hold ~100 MB
+            _DECODE_CASES.pop(next(iter(_DECODE_CASES)))
+        _DECODE_CASES[k] = DecodeCase(*key, **kw)
+    return _DECODE_CASES[k]
+
+
+# ---- grad-norm sum of squares ----------------------------------------------
+SUMSQ_CHUNK = 1 << 20                        # multi_sumsq in bindings.hip
+SUMSQ_GRID = 2048                            # galv_grid's cap
+SUMSQ_SIZES = [1, 3, 4, 5, 7, SUMSQ_CHUNK - 1, SUMSQ_CHUNK, SUMSQ_CHUNK + 1,
+               SUMSQ_CHUNK + 5, 2 * SUMSQ_CHUNK + 3]
+SUMSQ_OFFSETS = [0, 1, 2, 3, 123]
+SUMSQ_MANY = [5] * 2100
+
+
+def sumsq_inputs(sizes, offsets=0, seed=0):
+    """-> flat fp32 buffer and the (start, n) span of every tensor in it.
+    Tensor i starts `offsets[i]` elements after a 4-element boundary (the
+    optimizer passes views, so the 16-byte loads are in general only 4-byte
+    aligned).  randn everywhere; values of +-(1000..2000) planted in each
+    tensor's first and last element, its last n & 3 elements and on both
+    sides of every 2^20 boundary.  In a list longer than the grid cap only
+    the tensors past the cap carry planted values."""
+    g = _gen(9900 + seed)
+    if isinstance(offsets, int):
+        offsets = [offsets] * len(sizes)
+    spans, end = [], 0
+    for n, off in zip(sizes, offsets):
+        start = ((end + 3) & ~3) + off
+        spans.append((start, n))
+        end = start + n
+    flat = torch.randn(end + 4, generator=g)
+    j = 0
+    for i, (start, n) in enumerate(spans):
+        if n == 0 or (len(sizes) > SUMSQ_GRID and i < SUMSQ_GRID - 8):
+            continue
+        idx = {0, n - 1} | set(range(n - (n & 3), n))
+        for c in range(SUMSQ_CHUNK, n, SUMSQ_CHUNK):
+            idx |= {c - 1, c}
+        for k in sorted(idx):
+            flat[start + k] = (1000.0 + 37 * (j % 27)) * (1 - 2 * (j % 2))
+            j += 1
+    return flat, spans
+
+
+def sumsq_views(flat, spans, shift=0):
+    return [flat[s - shift:s - shift + n] for s, n in spans]
+
+
+def sumsq_lists():
+    """(id, sizes, offset) of every list both test files run: each size
+    alone and all in one list at every view offset, the list past the grid
+    cap, and lists with zero-element tensors."""
+    out = []
+    for off in SUMSQ_OFFSETS:
+        out += [(f"n{n}-off{off}", [n], off) for n in SUMSQ_SIZES]
+        out.append((f"all-off{off}", list(SUMSQ_SIZES), off))
+    out.append(("many", list(SUMSQ_MANY), 0))
+    out.append(("many-off3", list(SUMSQ_MANY), 3))
+    out.append(("zero-middle", [5, 0, SUMSQ_CHUNK + 1, 0, 7], 1))
+    out.append(("zero-only", [0, 0, 0], 0))
+    return out
+
+
+def decode_params(groups):
+    """(b, hq, hkv, d, max_s, n, start) over DECODE_DIMS x DECODE_STARTS."""
+    return [(b, hq, hkv, d, max_s, n, start)
+            for b, hq, hkv, max_s, n in groups
+            for d in DECODE_DIMS for start in DECODE_STARTS]
+
+
+def decode_graph_params():
+    return [(b, hq, hkv, d, max_s, n)
+            for b, hq, hkv, max_s, n in DECODE_GRAPH for d in DECODE_DIMS]
+
+
+DECODE_EXTREME = (1, 4, 2, 1280, 257)        # 3 chunks

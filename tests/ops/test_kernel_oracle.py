@@ -529,3 +529,211 @@ def test_grouped_gemm_reference_passes(counts, K, N):
         mut = dw64.clone()
         mut[e] -= torch.outer(ko.f64(a)[last], ko.f64(dc)[last])
         accum_mutant(mut, dw32, dw64, "grouped dW: one row lost")
+
+
+# ---------------------------------------------------------------------------
+# decode attention
+# ---------------------------------------------------------------------------
+MISS = {}            # mutant -> smallest err/bound seen, for the summary test
+
+
+def _miss(name, r):
+    MISS[name] = min(MISS.get(name, math.inf), r)
+
+
+def _decode_apply(c, w, v=None):
+    """o of the per-position weights w [b, hq, n] (rows need not sum to 1
+    before: they are normalised here unless v is given with w as is)."""
+    qg, _, v0 = ko._decode_window(c.q, c.kc, c.vc, c.cur, c.start)
+    b, hkv, rep, d = qg.shape
+    v = v0 if v is None else v
+    w = w / w.sum(-1, keepdim=True)
+    return (w.reshape(b, hkv, rep, -1) @ v).reshape(b, c.hq, d)
+
+
+def decode_mutants(c):
+    """name -> the fp64 oracle of c with one planted defect, for every
+    defect that the case's shape admits."""
+    n, nc, ch = c.n, c.nc, c.chunk
+    w, s = c.aux["w"], c.aux["s"]
+    last = (n - 1) // ch                     # last chunk that holds a row
+    out = {}
+
+    def drop(name, sel, mult=0.0):
+        m = torch.ones(n, dtype=torch.float64)
+        m[sel] = mult
+        out[name] = _decode_apply(c, w * m)
+
+    if n >= 2:
+        drop("last position dropped", n - 1)
+        drop("first position dropped", 0)
+    if c.start:
+        out["start ignored"] = ko.decode_attn(c.q, c.kc, c.vc, c.cur,
+                                              c.scale, 0)[0]
+    if last >= 1:
+        drop("boundary: last row of chunk 0 lost", ch - 1)
+        drop("boundary: first row of the last chunk lost", last * ch)
+        drop("boundary: row counted in both chunks", ch, 2.0)
+        drop("a whole chunk lost", slice(ch, min(2 * ch, n)))
+        cid = torch.arange(n) // ch
+        e = torch.exp(s - c.aux["m"][..., None])
+        # every chunk relative to its own max, summed without exp(m_c - gm)
+        m_c = torch.stack([s[..., cid == j].amax(-1)
+                           for j in range(last + 1)], -1)
+        out["merge without reweighting"] = _decode_apply(
+            c, torch.exp(s - m_c[..., cid]))
+        # normalised by the last chunk's l alone
+        out["merge normalised by the last l"] = \
+            _decode_apply(c, e) * (e.sum(-1) / e[..., cid == last].sum(-1)
+                                   )[..., None]
+    if c.hkv > 1 and c.hq > c.hkv:
+        idx = torch.arange(c.hq) % c.hkv
+        out["GQA h % hkv"] = ko.decode_attn(
+            c.q, c.kc[:, :, idx], c.vc[:, :, idx], c.cur, c.scale,
+            c.start)[0]
+    vn = ko.f64(c.vc)[:, c.start + 1:c.cur + 1]
+    if vn.shape[1] < n:                      # cur == max_s: nothing beyond
+        vn = torch.cat([vn, torch.zeros_like(vn[:, :1])], 1)
+    out["V read at p + 1"] = _decode_apply(c, w, vn.permute(0, 2, 1, 3))
+    if ch > 256:
+        drop("second stripe lost", (torch.arange(n) % ch) >= 256)
+    return out
+
+
+def _decode_check(c, with_ref=True):
+    if with_ref:
+        elem_ok(c.ref32(), c.o, c.sc, f"decode {c.tag}")
+    # the needles carry the weight: in no head less than half of it
+    rel = ko.decode_needles(c.b, c.hq, c.d, c.n, c.max_len)
+    assert float(c.aux["w"][..., rel].sum(-1).min()) > 0.5
+    for name, mut in decode_mutants(c).items():
+        r = ko.elem_excess(mut.to(torch.bfloat16), c.o, c.sc)
+        print(f"[mutant] decode {c.tag}: {name}: err/bound = {r:.3g}")
+        _miss("decode: " + name, r)
+        assert r >= MUTANT_MARGIN, f"mutant passes: {name} {c.tag} {r}"
+
+
+@pytest.mark.parametrize(
+    "b,hq,hkv,d,max_s,n,start",
+    ko.decode_params(ko.DECODE_SINGLE + ko.DECODE_SPLIT), ids=_ids)
+def test_decode_reference_passes_mutants_miss(b, hq, hkv, d, max_s, n, start):
+    c = ko.decode_case(b, hq, hkv, d, max_s, n, start)
+    assert c.nc == (1 if (b * hq >= 256 or n <= 128) else -(-n // c.chunk))
+    _decode_check(c)
+
+
+@pytest.mark.parametrize("b,hq,hkv,d,max_s,n,start",
+                         ko.decode_params(ko.DECODE_LDS), ids=_ids)
+def test_decode_lds_cap_mutants_miss(b, hq, hkv, d, max_s, n, start):
+    """The fp32 reference expands the cache to 32 heads (1 GiB at these
+    shapes), so it runs on one start per head dim; the mutants on all."""
+    c = ko.decode_case(b, hq, hkv, d, max_s, n, start)
+    assert (c.nc, c.chunk) == ((1, 8192) if n == 8192 else (2, 4097))
+    _decode_check(c, with_ref=(start == 0) == (d == 64))
+
+
+@pytest.mark.parametrize("b,hq,hkv,d,max_s,n", ko.decode_graph_params(),
+                         ids=_ids)
+def test_decode_graph_reference_passes_mutants_miss(b, hq, hkv, d, max_s, n):
+    c = ko.decode_case(b, hq, hkv, d, max_s, n,
+                       max_len=ko.DECODE_GRAPH_MAX_LEN)
+    assert c.nc == 16 and c.chunk == -(-n // 16)
+    _decode_check(c)
+
+
+def test_decode_chunks_mirror_the_binding():
+    assert ko.decode_chunks(8, 32, 300) == (1, 300)
+    assert ko.decode_chunks(1, 4, 128) == (1, 128)
+    assert ko.decode_chunks(1, 4, 129) == (2, 65)
+    assert ko.decode_chunks(1, 4, 257) == (3, 86)
+    assert ko.decode_chunks(1, 4, 1025) == (9, 114)
+    assert ko.decode_chunks(1, 8, 257) == (3, 86)
+    assert ko.decode_chunks(8, 32, 8192) == (1, 8192)
+    assert ko.decode_chunks(8, 32, 8193) == (2, 4097)
+    assert ko.decode_chunks(1, 4, 17, 2048) == (16, 2)
+    assert ko.decode_chunks(1, 4, 1, 2048) == (16, 1)
+    assert ko.decode_chunks(1, 1, 100000) == (512, 196)
+
+
+@pytest.mark.parametrize("d", ko.DECODE_DIMS)
+def test_decode_extreme_scores_reference_passes(d):
+    b, hq, hkv, max_s, n = ko.DECODE_EXTREME
+    c = ko.decode_case(b, hq, hkv, d, max_s, n, extreme=True)
+    s = c.aux["s"]
+    assert float(s[:, 0].max()) < -100
+    assert float(s[:, 1:].amax(-1).min()) > 55
+    assert float(s[:, 1:].amin(-1).max()) < -55
+    elem_ok(c.ref32(), c.o, c.sc, f"decode extreme d={d}")
+    # still a test: the last position dropped misses by the margin
+    m = torch.ones(n, dtype=torch.float64)
+    m[s[0, 1].argmax()] = 0
+    r = ko.elem_excess(_decode_apply(c, c.aux["w"] * m).bfloat16(), c.o, c.sc)
+    assert r >= MUTANT_MARGIN, r
+
+
+# ---------------------------------------------------------------------------
+# grad-norm sum of squares
+# ---------------------------------------------------------------------------
+def sumsq_mutants(flat, spans, off):
+    """name -> fp64 [1] of the sum of squares with one planted defect."""
+    C = ko.SUMSQ_CHUNK
+    xs = [ko.f64(x) for x in ko.sumsq_views(flat, spans)]
+    full = ko.sumsq(xs)
+    out = {}
+    if any(len(x) & 3 for x in xs):
+        out["n & 3 tail dropped"] = ko.sumsq(
+            [x[:len(x) & ~3] for x in xs])
+    big = [x for x in xs if len(x) > C]
+    if big:
+        out["element at a 2^20 boundary dropped"] = full - big[-1][C] ** 2
+        out["element at a 2^20 boundary doubled"] = full + big[0][C - 1] ** 2
+    if off:
+        out["view offset ignored"] = ko.sumsq(
+            ko.sumsq_views(flat, spans, shift=off))
+    chunks = [x[o:o + C] for x in xs for o in range(0, len(x), C)]
+    if len(chunks) > ko.SUMSQ_GRID:
+        out["chunks past 2047 dropped"] = ko.sumsq(chunks[:ko.SUMSQ_GRID])
+    if any(len(x) for x in xs):
+        out["sum of |x|"] = sum(x.abs().sum() for x in xs).reshape(1)
+    return out
+
+
+@pytest.mark.parametrize("name,sizes,off", ko.sumsq_lists(),
+                         ids=[c[0] for c in ko.sumsq_lists()])
+def test_sumsq_reference_passes_mutants_miss(name, sizes, off):
+    flat, spans = ko.sumsq_inputs(sizes, off)
+    xs = ko.sumsq_views(flat, spans)
+    assert all(x.data_ptr() % 16 == (4 * off) % 16 for x in xs if len(x))
+    o64, r32 = ko.sumsq(xs), ko.sumsq_ref32(xs)
+    ko.assert_accum(r32, r32, o64, f"sumsq {name}")
+    e_ref = float((ko.f64(r32) - o64).abs())
+    print(f"[floor] sumsq {name}: E_ref {e_ref:.3g}  oracle {float(o64):.6g}"
+          f"  relative {e_ref / max(float(o64), 1e-300):.2g}")
+    if not sum(sizes):
+        assert float(o64) == 0.0 and float(r32) == 0.0
+    for mname, mut in sumsq_mutants(flat, spans, off).items():
+        r = ko.accum_excess(mut, r32, o64)
+        print(f"[mutant] sumsq {name}: {mname}: err/bound = {r:.3g}")
+        _miss("sumsq: " + mname, r)
+        assert r >= MUTANT_MARGIN, f"mutant passes: {mname} {name} {r}"
+
+
+def test_sumsq_mutant_coverage():
+    """Every listed defect is planted by at least one list."""
+    seen = set()
+    for _, sizes, off in ko.sumsq_lists():
+        if max(sizes) <= 7 or len(sizes) > 1:
+            flat, spans = ko.sumsq_inputs(sizes, off)
+            seen |= set(sumsq_mutants(flat, spans, off))
+    assert seen == {"n & 3 tail dropped", "element at a 2^20 boundary dropped",
+                    "element at a 2^20 boundary doubled",
+                    "view offset ignored", "chunks past 2047 dropped",
+                    "sum of |x|"}
+
+
+def test_smallest_mutant_miss():
+    """Printed for the record: the smallest err/bound of each decode and
+    sumsq mutant over the cases run before this test in the session."""
+    for name in sorted(MISS):
+        print(f"[smallest miss] {name}: {MISS[name]:.3g}")
+    assert all(r >= MUTANT_MARGIN for r in MISS.values())
