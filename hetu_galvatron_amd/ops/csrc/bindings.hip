@@ -58,6 +58,8 @@ void qkv_grad_finish_launch(__bf16*, const __bf16*, const __bf16*, const float*,
 int multi_sumsq_grid(int);
 void multi_sumsq_launch(const long*, int, float*, hipStream_t);
 void decode_attn_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, int, float, const int*, hipStream_t);
+int decode_batched_tile();
+void decode_attn_batched_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
 
 namespace {
 
@@ -759,7 +761,8 @@ struct DecodeDims {
 };
 
 DecodeDims decode_dims(const Tensor& q, const Tensor& k_cache,
-                       const Tensor& v_cache, const char* who) {
+                       const Tensor& v_cache, const char* who,
+                       bool same_rows = true) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
               who, ": q must be bf16 [b,hq,d], contiguous on GPU, got ",
               q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
@@ -769,7 +772,8 @@ DecodeDims decode_dims(const Tensor& q, const Tensor& k_cache,
               k_cache.device(), " ", k_cache.sizes(), " strides ",
               k_cache.strides());
   TORCH_CHECK(is_bf16(k_cache) && k_cache.dim() == 4 &&
-                  k_cache.size(0) == q.size(0) &&
+                  (same_rows ? k_cache.size(0) == q.size(0)
+                             : k_cache.size(0) > 0) &&
                   k_cache.size(3) == q.size(2), who,
               ": k_cache must be bf16 [b,max_s,hkv,d] with q's batch and "
               "head dim, got ", k_cache.scalar_type(), " ", k_cache.sizes(),
@@ -860,6 +864,69 @@ Tensor decode_attn_graph(const Tensor& q, const Tensor& k_cache,
                      ws.data_ptr<float>(), n_chunks, b, hq, hkv, max_s,
                      (int)max_len, d, (float)scale,
                      cur_len_dev.data_ptr<int>(), cur_stream());
+  return o;
+}
+
+// Batched decode: row i of q [n,hq,d] attends to positions
+// [max(0, len_i - window), len_i) of row slots[i] of the caches
+// [S,max_s,hkv,d], len_i = min(lengths[i], max_len).  lengths and slots stay
+// on the device; launch geometry comes from the host arguments alone.
+// n_chunks = 0 chooses the split; a positive value is used as given, capped
+// so that a chunk is at least one key tile.
+Tensor decode_attn_batched(const Tensor& q, const Tensor& k_cache,
+                           const Tensor& v_cache, const Tensor& lengths,
+                           const Tensor& slots, int64_t max_len, double scale,
+                           int64_t window, int64_t n_chunks) {
+  const char* who = "decode_attn_batched";
+  const DecodeDims g = decode_dims(q, k_cache, v_cache, who, false);
+  const int n = g.b, hq = g.hq, d = g.d, max_s = g.max_s, hkv = g.hkv;
+  const int64_t S = k_cache.size(0);
+  TORCH_CHECK(n >= 1 && n <= 65535 && hkv <= 65535 && S < (1LL << 31), who,
+              ": n (rows of q) and hkv must be in [1, 65535] and the cache "
+              "rows below 2^31, got q ", q.sizes(), " k_cache ",
+              k_cache.sizes());
+  TORCH_CHECK(hq / hkv <= 16, who, ": qpg = hq / hkv must be <= 16, got hq ",
+              hq, " hkv ", hkv);
+  auto check_i32 = [&](const Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == q.device() &&
+                    t.scalar_type() == at::kInt && t.is_contiguous() &&
+                    t.dim() == 1 && t.size(0) == n, who, ": ", name,
+                " must be int32 [n] contiguous on q's GPU (n = ", n,
+                "), got ", t.scalar_type(), " ", t.sizes(), " on ",
+                t.device());
+  };
+  check_i32(lengths, "lengths");
+  check_i32(slots, "slots");
+  TORCH_CHECK(max_len >= 1 && max_len <= max_s, who,
+              ": max_len must be in [1, max_s], got ", max_len,
+              " for k_cache ", k_cache.sizes());
+  TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
+  TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
+  if (window >= max_len) window = 0;   // such a window cuts nothing off
+  const int tile = decode_batched_tile();
+  const int64_t span = window > 0 ? std::min(max_len, window) : max_len;
+  if (n_chunks == 0) {
+    // about 512 workgroups from the n*hkv rows, chunks of >= 256 positions
+    n_chunks = std::max<int64_t>(1, 512 / ((int64_t)n * hkv));
+    n_chunks = std::min<int64_t>(n_chunks, (span + 255) / 256);
+  }
+  n_chunks = std::min<int64_t>(n_chunks, (span + tile - 1) / tile);
+  const int64_t chunk =
+      ((span + n_chunks - 1) / n_chunks + tile - 1) / tile * tile;
+  n_chunks = (span + chunk - 1) / chunk;   // drop chunks no row can reach
+  auto o = at::empty_like(q);
+  Tensor ws;
+  float* ws_ptr = nullptr;
+  if (n_chunks > 1) {
+    ws = at::empty({(int64_t)n * hq * n_chunks * (d + 2)},
+                   q.options().dtype(at::kFloat));
+    ws_ptr = ws.data_ptr<float>();
+  }
+  decode_attn_batched_launch(bfp(q), bfp(k_cache), bfp(v_cache), bfp_mut(o),
+                             ws_ptr, lengths.data_ptr<int>(),
+                             slots.data_ptr<int>(), n, hq, hkv, (int)S, max_s,
+                             (int)max_len, (int)window, (int)chunk,
+                             (int)n_chunks, d, (float)scale, cur_stream());
   return o;
 }
 
@@ -1175,6 +1242,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_grad_finish_", &qkv_grad_finish_, py::arg("dqkv"), py::arg("dk_exp"), py::arg("dv_exp"), py::arg("cos") = py::none(), py::arg("sin") = py::none());
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cur_len"), py::arg("scale"), py::arg("start") = 0);
   m.def("decode_attn_graph", &decode_attn_graph);
+  m.def("decode_attn_batched", &decode_attn_batched, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("mfma_probe", &mfma_probe);
   m.def("ce_max", &ce_max);
   m.def("ce_sum_target", &ce_sum_target);

@@ -674,6 +674,10 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
             and q.shape[-1] in (64, 128):
         return get_ext().decode_attn(q.contiguous(), k_cache, v_cache,
                                      int(cur_len), float(scale), int(start))
+    return _decode_attention_torch(q, k_cache, v_cache, cur_len, scale, start)
+
+
+def _decode_attention_torch(q, k_cache, v_cache, cur_len, scale, start):
     b, hq, d = q.shape
     hkv = k_cache.shape[2]
     k = k_cache[:, start:cur_len].float()
@@ -686,3 +690,49 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     w = att.softmax(-1)
     o = torch.einsum("bhs,bshd->bhd", w, v)
     return o.to(q.dtype)
+
+
+@torch.no_grad()
+def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
+                             v_cache: torch.Tensor, lengths: torch.Tensor,
+                             slots: torch.Tensor = None, max_len: int = None,
+                             softmax_scale=None, window=None) -> torch.Tensor:
+    """Decode attention for a batch of rows with their own lengths and cache
+    rows (continuous-batching serving).
+
+    q: [n, hq, d]; k_cache/v_cache: [S, max_s, hkv, d]; lengths: int32 [n],
+    the attended length of each row, newest token included; slots: int32
+    [n], the cache row of each q row (None: row i uses cache row i, n == S).
+    Row i attends to [0, lengths[i]) or the last `window` of them.  max_len
+    (None: max_s) bounds every length and sizes the launch.
+
+    Native CDNA4 kernel on GPU bf16 with d in (64, 128) and hq/hkv <= 16
+    (decode_attn_batched.hip): one launch for the whole batch, each K/V row
+    read once per GQA group, lengths and slots read on the device — no host
+    read-back, so a captured graph replays after they change in place; a
+    length above max_len is clamped, a row with length <= 0 or a slot
+    outside [0, S) gives zeros.  Elsewhere a loop over rows through the torch
+    arithmetic of `decode_attention` (reads lengths and slots on the host).
+    """
+    n, hq, d = q.shape
+    S, max_s, hkv = k_cache.shape[:3]
+    scale = softmax_scale if softmax_scale is not None else d ** -0.5
+    max_len = max_s if max_len is None else int(max_len)
+    if slots is None:
+        assert n == S, "slots=None needs one q row per cache row"
+        slots = torch.arange(n, dtype=torch.int32, device=q.device)
+    if q.is_cuda and native_available() and q.dtype == torch.bfloat16 \
+            and d in (64, 128) and hq // hkv <= 16:
+        return get_ext().decode_attn_batched(
+            q.contiguous(), k_cache, v_cache, lengths, slots, max_len,
+            float(scale), int(window or 0), 0)
+    out = torch.zeros_like(q)
+    for i, (cur, s) in enumerate(zip(lengths.tolist(), slots.tolist())):
+        cur = min(cur, max_len)
+        if cur <= 0 or not 0 <= s < S:
+            continue
+        start = max(0, cur - window) if window else 0
+        out[i:i + 1] = _decode_attention_torch(
+            q[i:i + 1], k_cache[s:s + 1], v_cache[s:s + 1], cur, scale,
+            start)
+    return out

@@ -3,14 +3,16 @@
 Requests join and leave between decode steps (vLLM-style scheduling
 semantics, reference has no serving path): each slot owns a contiguous
 row of the persistent KV cache with its own length, the per-step linears
-(qkv, proj, mlp, head) are batched across every active slot, and
-attention runs per slot on its cache row ([slot:slot+1] is a contiguous
-view — no copies).
+(qkv, proj, mlp, head) are batched across every active slot.
 
-v1 performance note: per-slot attention means n_active kernel launches
-per layer; the batched-attention upgrade is a per-row cur_len variant of
-the decode kernel (roadmap).  RoPE at mixed positions is applied with a
-pure-torch broadcast (per-slot table rows), not the shared-table kernel.
+Attention has two paths.  The default runs per slot on its cache row
+([slot:slot+1] is a contiguous view — no copies): n_active cache writes
+and `decode_attention` launches per layer.  `batched_attention=True` does
+one indexed cache write and one `decode_attention_batched` call per layer
+for all active slots: per-row lengths and cache rows are device tensors
+built once per step, and each K/V row is read once per GQA group.  RoPE at
+mixed positions is applied with a pure-torch broadcast (per-slot table
+rows), not the shared-table kernel.
 """
 from __future__ import annotations
 
@@ -18,7 +20,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..ops import decode_attention, flash_attention_fwd_only
+from ..ops import (decode_attention, decode_attention_batched,
+                   flash_attention_fwd_only)
 from .inference import GalvatronGenerator, KVCache
 
 __all__ = ["ContinuousBatchingEngine"]
@@ -43,7 +46,9 @@ def _rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
 class ContinuousBatchingEngine:
     """Greedy decode over a slot pool (world=1 topology)."""
 
-    def __init__(self, model, max_slots: int = 8, max_seq: int = 4096):
+    def __init__(self, model, max_slots: int = 8, max_seq: int = 4096,
+                 batched_attention: bool = False):
+        self.batched_attention = batched_attention
         self.gen = GalvatronGenerator(model, max_batch=max_slots,
                                       max_seq=max_seq)
         m = model.cfg.model
@@ -151,6 +156,11 @@ class ContinuousBatchingEngine:
         ids = torch.tensor([[self.last_tok[s] for s in active]],
                            device=dev)                      # [1, n]
         pos = torch.tensor([self.lengths[s] for s in active], device=dev)
+        if self.batched_attention:
+            slot_t = torch.tensor(active, device=dev)
+            slot32 = slot_t.int()
+            lengths_t = (pos + 1).int()      # the new token is attended too
+            max_len = max(self.lengths[s] for s in active) + 1
         h = gen.embedding.word_embeddings(ids.transpose(0, 1))  # [1, n, hd]
         for li, layer in enumerate(gen.layers):
             attn = layer.attention
@@ -165,16 +175,15 @@ class ContinuousBatchingEngine:
                 il = getattr(attn, "rope_interleaved", False)
                 q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
                 k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
-            outs = []
-            for i, s in enumerate(active):
-                L = self.lengths[s]
-                self.cache.k[li][s, L] = k[0, i]
-                self.cache.v[li][s, L] = v[0, i]
-                o = decode_attention(q[:, i], self.cache.k[li][s:s + 1],
-                                     self.cache.v[li][s:s + 1], L + 1,
-                                     softmax_scale=gen.scale,
-                                     window=getattr(gen, "window", None))
-                outs.append(o)
+            if self.batched_attention:
+                self.cache.k[li][slot_t, pos] = k[0]
+                self.cache.v[li][slot_t, pos] = v[0]
+                outs = [decode_attention_batched(
+                    q[0], self.cache.k[li], self.cache.v[li], lengths_t,
+                    slot32, max_len=max_len, softmax_scale=gen.scale,
+                    window=getattr(gen, "window", None))]
+            else:
+                outs = self._attend_per_slot(li, active, q, k, v)
             o = torch.cat(outs, 0).unsqueeze(0).reshape(1, len(active), -1)
             h = residual + attn.linear_proj(o)
             residual = h
@@ -196,6 +205,19 @@ class ContinuousBatchingEngine:
                                         and t == self.eos[s]):
                 self.release(rid)
         return out
+
+    def _attend_per_slot(self, li, active, q, k, v):
+        outs = []
+        for i, s in enumerate(active):
+            L = self.lengths[s]
+            self.cache.k[li][s, L] = k[0, i]
+            self.cache.v[li][s, L] = v[0, i]
+            o = decode_attention(q[:, i], self.cache.k[li][s:s + 1],
+                                 self.cache.v[li][s:s + 1], L + 1,
+                                 softmax_scale=self.gen.scale,
+                                 window=getattr(self.gen, "window", None))
+            outs.append(o)
+        return outs
 
     def _sample(self, logits_row: torch.Tensor, slot: int) -> int:
         temp, g = self.samplers[slot]

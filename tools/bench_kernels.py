@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -234,6 +234,51 @@ def bench_qkv_varlen(iters, repeats=9, composition_only=False):
                   f" [{lo*1e3:.3f}, {hi*1e3:.3f}]")
 
 
+def bench_decode_batched(iters, repeats=9, loop_only=False):
+    """One ops.decode_attention_batched call vs the loop of per-slot
+    ops.decode_attention calls it replaces in the serving engine, and vs
+    decode_attn at b = n (uniform lengths only): h32/8 d128 bf16, n slots of
+    a [n, 4096, 8, 128] cache, lengths uniform 4096 or a geometric ladder
+    from 1 to 4096.  GB/s counts each attended K and V row once.
+    loop_only times only the loop and decode_attn (to time another build of
+    the extension that predates the batched op with the same code)."""
+    from hetu_galvatron_amd import ops
+    hq, hkv, d, max_s = 32, 8, 128, 4096
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in (8, 32):
+        q = torch.randn(n, hq, d, device="cuda", generator=g).bfloat16()
+        kc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        vc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        slots = torch.arange(n, dtype=torch.int32, device="cuda")
+        ladder = [max(1, round(max_s ** (i / (n - 1)))) for i in range(n)]
+        for label, lens in (("uniform", [max_s] * n), ("mixed", ladder)):
+            lengths = torch.tensor(lens, dtype=torch.int32, device="cuda")
+            gb = 2 * sum(lens) * hkv * d * 2 / 1e9
+
+            def loop():
+                return [ops.decode_attention(q[i:i + 1], kc[i:i + 1],
+                                             vc[i:i + 1], L)
+                        for i, L in enumerate(lens)]
+
+            def batched():
+                return ops.decode_attention_batched(q, kc, vc, lengths, slots,
+                                                    max_len=max(lens))
+
+            rows = [("loop", loop)]
+            if label == "uniform":
+                rows.append(("decode_attn", lambda: ops.decode_attention(
+                    q, kc, vc, max_s)))
+            if not loop_only:
+                rows.append(("batched", batched))
+            for name, fn in rows:
+                t, lo, hi = median_of_windows(fn, iters, repeats)
+                print(f"decode-batched n{n:<2d} {label:7s} {name:11s} "
+                      f"{t*1e6:8.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]  "
+                      f"{gb/t:6.0f} GB/s")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -319,6 +364,8 @@ def main():
                     help="timed windows per row (varlen and qkv entries)")
     ap.add_argument("--dense-only", action="store_true",
                     help="varlen entry: time only the dense kernels")
+    ap.add_argument("--loop-only", action="store_true",
+                    help="decode-batched entry: skip the batched op")
     ap.add_argument("--composition-only", action="store_true",
                     help="qkv-varlen entry: time only the composition")
     args = ap.parse_args()
@@ -329,6 +376,8 @@ def main():
            "varlen": lambda it: bench_varlen(it, args.repeats,
                                              args.dense_only),
            "qkv": lambda it: bench_qkv(it, args.repeats),
+           "decode-batched": lambda it: bench_decode_batched(
+               it, args.repeats, args.loop_only),
            "qkv-varlen": lambda it: bench_qkv_varlen(
                it, args.repeats, args.composition_only)}
     if args.what == "all":
