@@ -1,7 +1,11 @@
 """HTTP serving entry: FastAPI over the continuous-batching engine.
 
   python -m hetu_galvatron_amd.cli.serve model.model_name=llama-3-8b \\
-      ckpt.load=/path/to/ckpt serve.port=8000 serve.max_slots=8
+      ckpt.load=/path/to/ckpt serve.port=8000 serve.max_slots=8 \\
+      [--kv-cache-dtype fp8]
+
+--kv-cache-dtype fp8 (or serve.kv_cache_dtype=fp8) keeps the KV cache in
+float8_e4m3fn and selects the batched decode attention it needs.
 
 POST /generate  {"prompt_ids": [..], "max_new_tokens": 64}
     -> {"request_id": r, "tokens": [...]}   (blocks until complete)
@@ -78,10 +82,14 @@ def main(argv=None):
 
     argv = list(sys.argv[1:] if argv is None else argv)
     opts = {"port": 8000, "host": "0.0.0.0", "max_slots": 8,
-            "max_seq": 4096}
+            "max_seq": 4096, "kv_cache_dtype": ""}
     rest = []
-    for a in argv:
-        if a.startswith("serve.") and "=" in a:
+    for i, a in enumerate(argv):
+        if a == "--kv-cache-dtype" and i + 1 < len(argv):
+            argv[i + 1] = "serve.kv_cache_dtype=" + argv[i + 1]
+        elif a.startswith("--kv-cache-dtype="):
+            opts["kv_cache_dtype"] = a.split("=", 1)[1]
+        elif a.startswith("serve.") and "=" in a:
             k, v = a[len("serve."):].split("=", 1)
             opts[k] = type(opts[k])(v)
         else:
@@ -105,8 +113,11 @@ def main(argv=None):
             state = hf_to_canonical(load_hf_checkpoint(cfg.ckpt.load),
                                     cfg.model)
             load_full_state(model.stage_model, state, cfg.model)
+    kv_dtype = opts["kv_cache_dtype"] or None
     engine = ContinuousBatchingEngine(model, max_slots=opts["max_slots"],
-                                      max_seq=opts["max_seq"])
+                                      max_seq=opts["max_seq"],
+                                      batched_attention=kv_dtype == "fp8",
+                                      kv_cache_dtype=kv_dtype)
     app = build_app(engine, threading.Lock())
     import uvicorn
     uvicorn.run(app, host=opts["host"], port=opts["port"])

@@ -60,6 +60,9 @@ void multi_sumsq_launch(const long*, int, float*, hipStream_t);
 void decode_attn_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, int, float, const int*, hipStream_t);
 int decode_batched_tile();
 void decode_attn_batched_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
+int decode_fp8_tile();
+void decode_attn_batched_fp8_launch(const __bf16*, const uint8_t*, const uint8_t*, const float*, const float*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
+void kv_append_fp8_launch(const __bf16*, const __bf16*, long, long, long, long, uint8_t*, uint8_t*, const float*, const float*, const int*, const int*, int, int, int, int, int, hipStream_t);
 
 namespace {
 
@@ -867,6 +870,24 @@ Tensor decode_attn_graph(const Tensor& q, const Tensor& k_cache,
   return o;
 }
 
+// The split of the batched decode kernels: n_chunks = 0 asks for about 512
+// workgroups from the n*hkv rows with chunks of >= 256 positions; a positive
+// value is capped so that a chunk is at least one key tile.  -> chunk (a
+// multiple of tile); n_chunks becomes the count that a row can reach.
+int64_t decode_batched_split(int n, int hkv, int64_t max_len, int64_t window,
+                             int tile, int64_t& n_chunks) {
+  const int64_t span = window > 0 ? std::min(max_len, window) : max_len;
+  if (n_chunks == 0) {
+    n_chunks = std::max<int64_t>(1, 512 / ((int64_t)n * hkv));
+    n_chunks = std::min<int64_t>(n_chunks, (span + 255) / 256);
+  }
+  n_chunks = std::min<int64_t>(n_chunks, (span + tile - 1) / tile);
+  const int64_t chunk =
+      ((span + n_chunks - 1) / n_chunks + tile - 1) / tile * tile;
+  n_chunks = (span + chunk - 1) / chunk;   // drop chunks no row can reach
+  return chunk;
+}
+
 // Batched decode: row i of q [n,hq,d] attends to positions
 // [max(0, len_i - window), len_i) of row slots[i] of the caches
 // [S,max_s,hkv,d], len_i = min(lengths[i], max_len).  lengths and slots stay
@@ -903,17 +924,8 @@ Tensor decode_attn_batched(const Tensor& q, const Tensor& k_cache,
   TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
   TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
   if (window >= max_len) window = 0;   // such a window cuts nothing off
-  const int tile = decode_batched_tile();
-  const int64_t span = window > 0 ? std::min(max_len, window) : max_len;
-  if (n_chunks == 0) {
-    // about 512 workgroups from the n*hkv rows, chunks of >= 256 positions
-    n_chunks = std::max<int64_t>(1, 512 / ((int64_t)n * hkv));
-    n_chunks = std::min<int64_t>(n_chunks, (span + 255) / 256);
-  }
-  n_chunks = std::min<int64_t>(n_chunks, (span + tile - 1) / tile);
-  const int64_t chunk =
-      ((span + n_chunks - 1) / n_chunks + tile - 1) / tile * tile;
-  n_chunks = (span + chunk - 1) / chunk;   // drop chunks no row can reach
+  const int64_t chunk = decode_batched_split(n, hkv, max_len, window,
+                                             decode_batched_tile(), n_chunks);
   auto o = at::empty_like(q);
   Tensor ws;
   float* ws_ptr = nullptr;
@@ -928,6 +940,153 @@ Tensor decode_attn_batched(const Tensor& q, const Tensor& k_cache,
                              (int)max_len, (int)window, (int)chunk,
                              (int)n_chunks, d, (float)scale, cur_stream());
   return o;
+}
+
+// ---- FP8 (e4m3) KV cache ---------------------------------------------------
+bool is_e4m3(const Tensor& t) {
+  return t.scalar_type() == at::kFloat8_e4m3fn;
+}
+const uint8_t* u8p(const Tensor& t) {
+  return static_cast<const uint8_t*>(t.data_ptr());
+}
+
+// caches: e4m3 [S, max_s, hkv, d] contiguous on `dev`, d 64 or 128
+void check_fp8_caches(const Tensor& k_cache, const Tensor& v_cache,
+                      c10::Device dev, int64_t d, const char* who) {
+  TORCH_CHECK(k_cache.is_cuda() && k_cache.device() == dev &&
+                  k_cache.is_contiguous() && is_e4m3(k_cache) &&
+                  k_cache.dim() == 4 && k_cache.size(0) > 0 &&
+                  k_cache.size(0) < (1LL << 31) && k_cache.size(3) == d &&
+                  reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0,
+              who, ": k_cache must be float8_e4m3fn [S,max_s,hkv,d], "
+              "contiguous and 16-byte aligned on ", dev, " with d = ", d,
+              ", got ", k_cache.scalar_type(), " ", k_cache.sizes(), " on ",
+              k_cache.device());
+  TORCH_CHECK(v_cache.is_cuda() && v_cache.device() == dev &&
+                  v_cache.is_contiguous() && is_e4m3(v_cache) &&
+                  v_cache.sizes() == k_cache.sizes() &&
+                  reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
+              who, ": v_cache must be float8_e4m3fn, contiguous, 16-byte "
+              "aligned and shaped like k_cache, got ", v_cache.scalar_type(),
+              " ", v_cache.sizes(), " on ", v_cache.device());
+  TORCH_CHECK(d == 64 || d == 128, who, ": head dim must be 64|128, got ", d);
+}
+
+// scale: none (ones) or fp32 [hkv] contiguous on `dev` -> pointer or null
+const float* fp8_scale_ptr(const c10::optional<Tensor>& t, c10::Device dev,
+                           int64_t hkv, const char* who, const char* name) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == dev &&
+                  t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                  t->dim() == 1 && t->size(0) == hkv, who, ": ", name,
+              " must be fp32 [hkv] contiguous on ", dev, " (hkv = ", hkv,
+              "), got ", t->scalar_type(), " ", t->sizes(), " on ",
+              t->device());
+  return t->data_ptr<float>();
+}
+
+void check_i32_rows(const Tensor& t, c10::Device dev, int64_t n,
+                    const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev &&
+                  t.scalar_type() == at::kInt && t.is_contiguous() &&
+                  t.dim() == 1 && t.size(0) == n, who, ": ", name,
+              " must be int32 [n] contiguous on ", dev, " (n = ", n,
+              "), got ", t.scalar_type(), " ", t.sizes(), " on ", t.device());
+}
+
+// decode_attn_batched on e4m3 caches: real K = stored * k_scale[h], likewise
+// V; a missing scale is ones.  Same split and the same refusals.
+Tensor decode_attn_batched_fp8(const Tensor& q, const Tensor& k_cache,
+                               const Tensor& v_cache,
+                               const c10::optional<Tensor>& k_scale,
+                               const c10::optional<Tensor>& v_scale,
+                               const Tensor& lengths, const Tensor& slots,
+                               int64_t max_len, double scale, int64_t window,
+                               int64_t n_chunks) {
+  const char* who = "decode_attn_batched_fp8";
+  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
+              who, ": q must be bf16 [n,hq,d], contiguous on GPU, got ",
+              q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
+  const int64_t n = q.size(0), hq = q.size(1), d = q.size(2);
+  check_fp8_caches(k_cache, v_cache, q.device(), d, who);
+  const int64_t S = k_cache.size(0), max_s = k_cache.size(1);
+  const int64_t hkv = k_cache.size(2);
+  TORCH_CHECK(n >= 1 && n <= 65535 && hkv >= 1 && hkv <= 65535 && hq > 0 &&
+                  hq % hkv == 0, who, ": n and hkv must be in [1, 65535] and "
+              "hq % hkv == 0, got q ", q.sizes(), " k_cache ",
+              k_cache.sizes());
+  TORCH_CHECK(hq / hkv <= 16, who, ": qpg = hq / hkv must be <= 16, got hq ",
+              hq, " hkv ", hkv);
+  const float* ks = fp8_scale_ptr(k_scale, q.device(), hkv, who, "k_scale");
+  const float* vs = fp8_scale_ptr(v_scale, q.device(), hkv, who, "v_scale");
+  check_i32_rows(lengths, q.device(), n, who, "lengths");
+  check_i32_rows(slots, q.device(), n, who, "slots");
+  TORCH_CHECK(max_len >= 1 && max_len <= max_s, who,
+              ": max_len must be in [1, max_s], got ", max_len,
+              " for k_cache ", k_cache.sizes());
+  TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
+  TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
+  if (window >= max_len) window = 0;   // such a window cuts nothing off
+  const int64_t chunk = decode_batched_split((int)n, (int)hkv, max_len,
+                                             window, decode_fp8_tile(),
+                                             n_chunks);
+  auto o = at::empty_like(q);
+  Tensor ws;
+  float* ws_ptr = nullptr;
+  if (n_chunks > 1) {
+    ws = at::empty({n * hq * n_chunks * (d + 2)},
+                   q.options().dtype(at::kFloat));
+    ws_ptr = ws.data_ptr<float>();
+  }
+  decode_attn_batched_fp8_launch(
+      bfp(q), u8p(k_cache), u8p(v_cache), ks, vs, bfp_mut(o), ws_ptr,
+      lengths.data_ptr<int>(), slots.data_ptr<int>(), (int)n, (int)hq,
+      (int)hkv, (int)S, (int)max_s, (int)max_len, (int)window, (int)chunk,
+      (int)n_chunks, (int)d, (float)scale, cur_stream());
+  return o;
+}
+
+// Quantise k, v [n,hkv,d] bf16 (any row and head stride that keeps 16-byte
+// alignment, contiguous last dim) and store them at
+// cache[slots[i], positions[i]]; rows outside the cache are skipped.
+void kv_append_fp8(const Tensor& k, const Tensor& v, Tensor& k_cache,
+                   Tensor& v_cache, const Tensor& slots,
+                   const Tensor& positions,
+                   const c10::optional<Tensor>& k_scale,
+                   const c10::optional<Tensor>& v_scale) {
+  const char* who = "kv_append_fp8";
+  auto check_new = [&](const Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && is_bf16(t) && t.dim() == 3 &&
+                    (t.size(2) == 1 || t.stride(2) == 1) &&
+                    t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+                    t.stride(0) >= 0 && t.stride(1) >= 0 &&
+                    reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                who, ": ", name, " must be bf16 [n,hkv,d] on GPU with a "
+                "contiguous last dim, row and head strides that are "
+                "multiples of 8 and a 16-byte aligned base, got ",
+                t.scalar_type(), " ", t.sizes(), " strides ", t.strides());
+  };
+  check_new(k, "k");
+  check_new(v, "v");
+  TORCH_CHECK(v.sizes() == k.sizes() && v.device() == k.device(), who,
+              ": v must be shaped like k on k's GPU, got ", v.sizes(),
+              " for k ", k.sizes());
+  const int64_t n = k.size(0), hkv = k.size(1), d = k.size(2);
+  check_fp8_caches(k_cache, v_cache, k.device(), d, who);
+  TORCH_CHECK(k_cache.size(2) == hkv && n <= 65535, who,
+              ": the caches must have k's hkv (", hkv, ") and n <= 65535, "
+              "got k_cache ", k_cache.sizes(), " for k ", k.sizes());
+  const float* ks = fp8_scale_ptr(k_scale, k.device(), hkv, who, "k_scale");
+  const float* vs = fp8_scale_ptr(v_scale, k.device(), hkv, who, "v_scale");
+  check_i32_rows(slots, k.device(), n, who, "slots");
+  check_i32_rows(positions, k.device(), n, who, "positions");
+  if (n == 0) return;
+  kv_append_fp8_launch(
+      bfp(k), bfp(v), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+      static_cast<uint8_t*>(k_cache.data_ptr()),
+      static_cast<uint8_t*>(v_cache.data_ptr()), ks, vs,
+      slots.data_ptr<int>(), positions.data_ptr<int>(), (int)n, (int)hkv,
+      (int)d, (int)k_cache.size(0), (int)k_cache.size(1), cur_stream());
 }
 
 Tensor mfma_probe(const Tensor& A, const Tensor& B, bool alt) {
@@ -1243,6 +1402,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cur_len"), py::arg("scale"), py::arg("start") = 0);
   m.def("decode_attn_graph", &decode_attn_graph);
   m.def("decode_attn_batched", &decode_attn_batched, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_batched_fp8", &decode_attn_batched_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("kv_append_fp8", &kv_append_fp8, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("positions"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("mfma_probe", &mfma_probe);
   m.def("ce_max", &ce_max);
   m.def("ce_sum_target", &ce_sum_target);

@@ -57,6 +57,7 @@
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
                              apply_to = function)
 #endif
+#include "decode_rows.h"
 
 namespace {
 
@@ -67,24 +68,6 @@ constexpr float DB_NEG = -1e30f;
 
 typedef __attribute__((ext_vector_type(4))) short db_short4;
 typedef __attribute__((address_space(3))) db_short4 db_lds_short4;
-
-// len, start and slot of a row from the device tables; len = 0 is "empty".
-struct DbRow {
-  int len, start, slot;
-};
-
-DEV_INLINE DbRow db_row(const int* __restrict__ lengths,
-                        const int* __restrict__ slots, int row, int S,
-                        int max_len, int window) {
-  const int len = min(lengths[row], max_len);
-  const int slot = slots[row];
-  const bool ok = len > 0 && slot >= 0 && slot < S;
-  DbRow r;
-  r.len = ok ? len : 0;
-  r.slot = ok ? slot : 0;
-  r.start = (ok && window > 0) ? max(0, len - window) : 0;
-  return r;
-}
 
 // K fragments and V rows of the wave's 32 keys from key k0 on.  FULL: all 32
 // are inside [.., p1).  Otherwise rows past p1 - 1 are read from row p1 - 1
@@ -118,14 +101,6 @@ DEV_INLINE void db_load(const __bf16* __restrict__ kb,
     }
     vr[i] = v;
   }
-}
-
-// Orders the wave's own LDS writes and reads of its V image against each
-// other (the lanes exchange data); LDS operations of one wave execute in
-// order, so no instruction is needed, only the compiler must not move them.
-DEV_INLINE void db_wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 template <int D>

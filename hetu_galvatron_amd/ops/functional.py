@@ -696,7 +696,9 @@ def _decode_attention_torch(q, k_cache, v_cache, cur_len, scale, start):
 def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
                              v_cache: torch.Tensor, lengths: torch.Tensor,
                              slots: torch.Tensor = None, max_len: int = None,
-                             softmax_scale=None, window=None) -> torch.Tensor:
+                             softmax_scale=None, window=None,
+                             k_scale: torch.Tensor = None,
+                             v_scale: torch.Tensor = None) -> torch.Tensor:
     """Decode attention for a batch of rows with their own lengths and cache
     rows (continuous-batching serving).
 
@@ -713,6 +715,10 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
     length above max_len is clamped, a row with length <= 0 or a slot
     outside [0, S) gives zeros.  Elsewhere a loop over rows through the torch
     arithmetic of `decode_attention` (reads lengths and slots on the host).
+
+    float8_e4m3fn caches (decode_attn_fp8.hip) hold real = stored * scale[h]
+    with k_scale / v_scale fp32 [hkv] (None: ones); q and the result stay
+    bf16.  The scales are ignored for caches of any other dtype.
     """
     n, hq, d = q.shape
     S, max_s, hkv = k_cache.shape[:3]
@@ -721,11 +727,27 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
     if slots is None:
         assert n == S, "slots=None needs one q row per cache row"
         slots = torch.arange(n, dtype=torch.int32, device=q.device)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
     if q.is_cuda and native_available() and q.dtype == torch.bfloat16 \
             and d in (64, 128) and hq // hkv <= 16:
+        if fp8:
+            return get_ext().decode_attn_batched_fp8(
+                q.contiguous(), k_cache, v_cache, k_scale, v_scale, lengths,
+                slots, max_len, float(scale), int(window or 0), 0)
         return get_ext().decode_attn_batched(
             q.contiguous(), k_cache, v_cache, lengths, slots, max_len,
             float(scale), int(window or 0), 0)
+    if fp8:
+        return _decode_attention_batched_fp8_torch(
+            q, k_cache, v_cache, lengths, slots, max_len, scale, window,
+            k_scale, v_scale)
+    return _decode_attention_batched_torch(q, k_cache, v_cache, lengths,
+                                           slots, max_len, scale, window)
+
+
+def _decode_attention_batched_torch(q, k_cache, v_cache, lengths, slots,
+                                    max_len, scale, window):
+    S = k_cache.shape[0]
     out = torch.zeros_like(q)
     for i, (cur, s) in enumerate(zip(lengths.tolist(), slots.tolist())):
         cur = min(cur, max_len)
@@ -736,3 +758,65 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
             q[i:i + 1], k_cache[s:s + 1], v_cache[s:s + 1], cur, scale,
             start)
     return out
+
+
+def _decode_attention_batched_fp8_torch(q, k_cache, v_cache, lengths, slots,
+                                        max_len, scale, window, k_scale=None,
+                                        v_scale=None):
+    """`decode_attention_batched` on e4m3 caches in torch: the row loop on
+    each row's window, dequantised to fp32 (exact)."""
+    S = k_cache.shape[0]
+    ks = 1.0 if k_scale is None else k_scale.float()[:, None]
+    vs = 1.0 if v_scale is None else v_scale.float()[:, None]
+    out = torch.zeros_like(q)
+    for i, (cur, s) in enumerate(zip(lengths.tolist(), slots.tolist())):
+        cur = min(cur, max_len)
+        if cur <= 0 or not 0 <= s < S:
+            continue
+        start = max(0, cur - window) if window else 0
+        out[i:i + 1] = _decode_attention_torch(
+            q[i:i + 1], k_cache[s:s + 1, start:cur].float() * ks,
+            v_cache[s:s + 1, start:cur].float() * vs, cur - start, scale, 0)
+    return out
+
+
+@torch.no_grad()
+def kv_cache_append(k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor,
+                    v_cache: torch.Tensor, slots: torch.Tensor,
+                    positions: torch.Tensor, k_scale: torch.Tensor = None,
+                    v_scale: torch.Tensor = None) -> None:
+    """Write new K/V rows into the serving caches:
+    cache[slots[i], positions[i]] = k[i] (v likewise).
+
+    k, v: [n, hkv, d] (any row and head stride, e.g. views of the packed qkv
+    output); caches [S, max_s, hkv, d]; slots, positions: int32 [n] on the
+    caches' device.  A row whose slot is outside [0, S) or whose position is
+    outside [0, max_s) is skipped.  float8_e4m3fn caches store
+    e4m3_rne(clamp(x / scale[h], -448, 448)) with k_scale / v_scale fp32
+    [hkv] (None: ones): one native launch for both tensors on the GPU
+    (kv_append_fp8_kernel in decode_attn_fp8.hip), torch elsewhere.  Caches
+    of any other dtype get a plain indexed copy in torch.
+    """
+    if k_cache.dtype == torch.float8_e4m3fn and k.is_cuda \
+            and native_available() and k.dtype == torch.bfloat16 \
+            and k.shape[-1] in (64, 128):
+        get_ext().kv_append_fp8(k, v, k_cache, v_cache, slots, positions,
+                                k_scale, v_scale)
+        return
+    _kv_cache_append_torch(k, v, k_cache, v_cache, slots, positions, k_scale,
+                           v_scale)
+
+
+def _kv_cache_append_torch(k, v, k_cache, v_cache, slots, positions,
+                           k_scale=None, v_scale=None):
+    S, max_s = k_cache.shape[:2]
+    keep = (slots >= 0) & (slots < S) & (positions >= 0) & (positions < max_s)
+    sl, ps = slots[keep].long(), positions[keep].long()
+    for x, cache, scale in ((k, k_cache, k_scale), (v, v_cache, v_scale)):
+        x = x[keep]
+        if cache.dtype == torch.float8_e4m3fn:
+            x = x.float()
+            if scale is not None:
+                x = x / scale.float()[:, None]
+            x = x.clamp(-448.0, 448.0)
+        cache[sl, ps] = x.to(cache.dtype)

@@ -20,13 +20,19 @@ from typing import List, Optional
 
 import torch
 
-from ..ops import decode_attention, flash_attention_fwd_only
+from ..ops import (decode_attention, flash_attention_fwd_only,
+                   kv_cache_append)
 
 __all__ = ["KVCache", "GalvatronGenerator", "GalvatronTPGenerator"]
 
 
 class KVCache:
-    """Per-layer bf16 K/V ring of shape [b, max_seq, hkv, d]."""
+    """Per-layer K/V ring of shape [b, max_seq, hkv, d], bf16 by default.
+
+    dtype=torch.float8_e4m3fn allocates byte caches with per-layer
+    dequantisation scales `k_scale[l]`, `v_scale[l]` (fp32 [hkv], ones;
+    real = stored * scale[h]); `write` then quantises through
+    `ops.kv_cache_append`."""
 
     def __init__(self, n_layers: int, b: int, max_seq: int, hkv: int, d: int,
                  device, dtype=torch.bfloat16):
@@ -34,12 +40,29 @@ class KVCache:
                   for _ in range(n_layers)]
         self.v = [torch.empty(b, max_seq, hkv, d, device=device, dtype=dtype)
                   for _ in range(n_layers)]
+        self.fp8 = dtype == torch.float8_e4m3fn
+        self.k_scale = self.v_scale = [None] * n_layers
+        if self.fp8:
+            self.k_scale = [torch.ones(hkv, device=device)
+                            for _ in range(n_layers)]
+            self.v_scale = [torch.ones(hkv, device=device)
+                            for _ in range(n_layers)]
         self.max_seq = max_seq
         self.cur_len = 0
 
     def write(self, layer: int, k: torch.Tensor, v: torch.Tensor) -> None:
         """k, v: [b, s_new, hkv, d] for positions [cur_len, cur_len + s_new)."""
         s = k.shape[1]
+        if self.fp8:
+            b = k.shape[0]
+            i32 = dict(dtype=torch.int32, device=k.device)
+            slots = torch.arange(b, **i32).repeat_interleave(s)
+            pos = torch.arange(self.cur_len, self.cur_len + s, **i32).repeat(b)
+            kv_cache_append(k.reshape(b * s, *k.shape[2:]),
+                            v.reshape(b * s, *v.shape[2:]), self.k[layer],
+                            self.v[layer], slots, pos, self.k_scale[layer],
+                            self.v_scale[layer])
+            return
         self.k[layer][:, self.cur_len:self.cur_len + s] = k
         self.v[layer][:, self.cur_len:self.cur_len + s] = v
 

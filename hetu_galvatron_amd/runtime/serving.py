@@ -13,6 +13,12 @@ for all active slots: per-row lengths and cache rows are device tensors
 built once per step, and each K/V row is read once per GQA group.  RoPE at
 mixed positions is applied with a pure-torch broadcast (per-slot table
 rows), not the shared-table kernel.
+
+`kv_cache_dtype="fp8"` (batched attention only) keeps the caches in
+float8_e4m3fn with static per-layer, per-head scales: new rows are quantised
+and scattered by one `kv_cache_append` per layer, decode attends to the
+bytes directly, and prefill attends to its fresh bf16 K/V through flash and
+writes the slot's rows through the same op.
 """
 from __future__ import annotations
 
@@ -21,7 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ..ops import (decode_attention, decode_attention_batched,
-                   flash_attention_fwd_only)
+                   flash_attention_fwd_only, kv_cache_append)
 from .inference import GalvatronGenerator, KVCache
 
 __all__ = ["ContinuousBatchingEngine"]
@@ -47,7 +53,17 @@ class ContinuousBatchingEngine:
     """Greedy decode over a slot pool (world=1 topology)."""
 
     def __init__(self, model, max_slots: int = 8, max_seq: int = 4096,
-                 batched_attention: bool = False):
+                 batched_attention: bool = False, kv_cache_dtype: str = None,
+                 kv_scales: torch.Tensor = None):
+        """kv_cache_dtype: None (the model's dtype) or "fp8"; kv_scales:
+        fp32 [n_layers, 2, hkv] dequantisation scales of the fp8 cache
+        (k, v per layer; None: ones)."""
+        if kv_cache_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_cache_dtype must be None or 'fp8', got "
+                             f"{kv_cache_dtype!r}")
+        if kv_cache_dtype == "fp8" and not batched_attention:
+            raise ValueError("kv_cache_dtype='fp8' needs "
+                             "batched_attention=True")
         self.batched_attention = batched_attention
         self.gen = GalvatronGenerator(model, max_batch=max_slots,
                                       max_seq=max_seq)
@@ -55,10 +71,19 @@ class ContinuousBatchingEngine:
         self.margs = m
         self.max_slots = max_slots
         self.max_seq = max_seq
-        dtype = next(self.gen.embedding.parameters()).dtype
+        dtype = torch.float8_e4m3fn if kv_cache_dtype == "fp8" \
+            else next(self.gen.embedding.parameters()).dtype
         self.cache = KVCache(len(self.gen.layers), max_slots, max_seq,
                              m.kv_heads, m.head_dim, self.gen._dev,
                              dtype=dtype)
+        if kv_scales is not None:
+            if not self.cache.fp8 or tuple(kv_scales.shape) != (
+                    len(self.gen.layers), 2, m.kv_heads):
+                raise ValueError("kv_scales must be [n_layers, 2, hkv] and "
+                                 "needs kv_cache_dtype='fp8'")
+            sc = kv_scales.to(self.gen._dev, torch.float32)
+            self.cache.k_scale = [sc[i, 0].contiguous() for i in range(len(sc))]
+            self.cache.v_scale = [sc[i, 1].contiguous() for i in range(len(sc))]
         self.lengths = [0] * max_slots          # attended tokens per slot
         self.budgets: Dict[int, int] = {}       # slot -> tokens remaining
         self.last_tok: Dict[int, int] = {}      # slot -> pending input token
@@ -159,6 +184,7 @@ class ContinuousBatchingEngine:
         if self.batched_attention:
             slot_t = torch.tensor(active, device=dev)
             slot32 = slot_t.int()
+            pos32 = pos.int()
             lengths_t = (pos + 1).int()      # the new token is attended too
             max_len = max(self.lengths[s] for s in active) + 1
         h = gen.embedding.word_embeddings(ids.transpose(0, 1))  # [1, n, hd]
@@ -176,12 +202,19 @@ class ContinuousBatchingEngine:
                 q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
                 k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
             if self.batched_attention:
-                self.cache.k[li][slot_t, pos] = k[0]
-                self.cache.v[li][slot_t, pos] = v[0]
+                cache = self.cache
+                if cache.fp8:
+                    kv_cache_append(k[0], v[0], cache.k[li], cache.v[li],
+                                    slot32, pos32, cache.k_scale[li],
+                                    cache.v_scale[li])
+                else:
+                    cache.k[li][slot_t, pos] = k[0]
+                    cache.v[li][slot_t, pos] = v[0]
                 outs = [decode_attention_batched(
-                    q[0], self.cache.k[li], self.cache.v[li], lengths_t,
+                    q[0], cache.k[li], cache.v[li], lengths_t,
                     slot32, max_len=max_len, softmax_scale=gen.scale,
-                    window=getattr(gen, "window", None))]
+                    window=getattr(gen, "window", None),
+                    k_scale=cache.k_scale[li], v_scale=cache.v_scale[li])]
             else:
                 outs = self._attend_per_slot(li, active, q, k, v)
             o = torch.cat(outs, 0).unsqueeze(0).reshape(1, len(active), -1)
@@ -255,5 +288,13 @@ class _SlotCache:
 
     def write(self, layer: int, k, v, pos: int) -> None:
         s = k.shape[1]
-        self.cache.k[layer][self.slot, pos:pos + s] = k[0]
-        self.cache.v[layer][self.slot, pos:pos + s] = v[0]
+        c = self.cache
+        if c.fp8:
+            i32 = dict(dtype=torch.int32, device=k.device)
+            kv_cache_append(k[0], v[0], c.k[layer], c.v[layer],
+                            torch.full((s,), self.slot, **i32),
+                            torch.arange(pos, pos + s, **i32),
+                            c.k_scale[layer], c.v_scale[layer])
+            return
+        c.k[layer][self.slot, pos:pos + s] = k[0]
+        c.v[layer][self.slot, pos:pos + s] = v[0]

@@ -279,6 +279,57 @@ def bench_decode_batched(iters, repeats=9, loop_only=False):
                       f"{gb/t:6.0f} GB/s")
 
 
+def bench_decode_batched_fp8(iters, repeats=9):
+    """ops.decode_attention_batched on e4m3 caches beside the same call on
+    bf16 caches, and ops.kv_cache_append (n = 32 rows, one launch) beside the
+    two index_put calls it replaces: the cases, method and GB/s (attended
+    bytes: one per element here, two for bf16) of bench_decode_batched."""
+    from hetu_galvatron_amd import ops
+    hq, hkv, d, max_s = 32, 8, 128, 4096
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in (8, 32):
+        q = torch.randn(n, hq, d, device="cuda", generator=g).bfloat16()
+        kc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        vc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        ks = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        vs = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        k8 = (kc.float() / ks[:, None]).to(torch.float8_e4m3fn)
+        v8 = (vc.float() / vs[:, None]).to(torch.float8_e4m3fn)
+        slots = torch.arange(n, dtype=torch.int32, device="cuda")
+        ladder = [max(1, round(max_s ** (i / (n - 1)))) for i in range(n)]
+        for label, lens in (("uniform", [max_s] * n), ("mixed", ladder)):
+            lengths = torch.tensor(lens, dtype=torch.int32, device="cuda")
+            rows = [("bf16", 2, lambda: ops.decode_attention_batched(
+                        q, kc, vc, lengths, slots, max_len=max(lens))),
+                    ("fp8", 1, lambda: ops.decode_attention_batched(
+                        q, k8, v8, lengths, slots, max_len=max(lens),
+                        k_scale=ks, v_scale=vs))]
+            for name, width, fn in rows:
+                gb = 2 * sum(lens) * hkv * d * width / 1e9
+                t, lo, hi = median_of_windows(fn, iters, repeats)
+                print(f"decode-batched-fp8 n{n:<2d} {label:7s} {name:5s} "
+                      f"{t*1e6:8.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]  "
+                      f"{gb/t:6.0f} GB/s")
+    n = 32
+    x = torch.randn(n, hkv, 6, d, device="cuda", generator=g).bfloat16()
+    k, v = x[:, :, 4], x[:, :, 5]            # views, as the engine's
+    pos = torch.randint(0, max_s, (n,), device="cuda", generator=g)
+
+    def index_put():
+        kc[slots.long(), pos] = k
+        vc[slots.long(), pos] = v
+
+    pos32 = pos.int()
+    for name, fn in (("index_put x2 (bf16)", index_put),
+                     ("kv_cache_append", lambda: ops.kv_cache_append(
+                         k, v, k8, v8, slots, pos32, ks, vs))):
+        t, lo, hi = median_of_windows(fn, iters, repeats)
+        print(f"kv-append n{n} {name:20s} {t*1e6:8.1f} us "
+              f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -378,6 +429,8 @@ def main():
            "qkv": lambda it: bench_qkv(it, args.repeats),
            "decode-batched": lambda it: bench_decode_batched(
                it, args.repeats, args.loop_only),
+           "decode-batched-fp8": lambda it: bench_decode_batched_fp8(
+               it, args.repeats),
            "qkv-varlen": lambda it: bench_qkv_varlen(
                it, args.repeats, args.composition_only)}
     if args.what == "all":
