@@ -62,6 +62,8 @@ int decode_batched_tile();
 void decode_attn_batched_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
 int decode_fp8_tile();
 void decode_attn_batched_fp8_launch(const __bf16*, const uint8_t*, const uint8_t*, const float*, const float*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
+int decode_paged_tile();
+void decode_attn_paged_launch(const __bf16*, const void*, const void*, const float*, const float*, bool, __bf16*, float*, const int*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
 void kv_append_fp8_launch(const __bf16*, const __bf16*, long, long, long, long, uint8_t*, uint8_t*, const float*, const float*, const int*, const int*, int, int, int, int, int, hipStream_t);
 
 namespace {
@@ -1089,6 +1091,105 @@ void kv_append_fp8(const Tensor& k, const Tensor& v, Tensor& k_cache,
       (int)d, (int)k_cache.size(0), (int)k_cache.size(1), cur_stream());
 }
 
+// ---- paged KV cache --------------------------------------------------------
+// What the two paged bindings share once q and the pools [P,page,hkv,d] are
+// checked: row i attends to [max(0, len_i - window), len_i) of table row
+// slots[i], position p at pool[page_table[slots[i], p / page], p % page].
+// The split is decode_batched_split on the row's tiles from its first 32-key
+// boundary: window + 31 positions with a window, max_len without (then
+// chunks and tiles are those of the contiguous bindings).
+Tensor decode_paged_run(const Tensor& q, const Tensor& k_cache,
+                        const Tensor& v_cache, const float* ks,
+                        const float* vs, bool fp8, const Tensor& page_table,
+                        const Tensor& lengths, const Tensor& slots,
+                        int64_t max_len, double scale, int64_t window,
+                        int64_t n_chunks, const char* who) {
+  const int64_t n = q.size(0), hq = q.size(1), d = q.size(2);
+  const int64_t P = k_cache.size(0), page = k_cache.size(1);
+  const int64_t hkv = k_cache.size(2);
+  TORCH_CHECK(n >= 1 && n <= 65535 && hkv >= 1 && hkv <= 65535 && hq > 0 &&
+                  hq % hkv == 0 && P < (1LL << 31), who,
+              ": n and hkv must be in [1, 65535], hq % hkv == 0 and the pool "
+              "below 2^31 pages, got q ", q.sizes(), " k_cache ",
+              k_cache.sizes());
+  TORCH_CHECK(hq / hkv <= 16, who, ": qpg = hq / hkv must be <= 16, got hq ",
+              hq, " hkv ", hkv);
+  TORCH_CHECK(page >= 32 && (page & (page - 1)) == 0, who,
+              ": page (k_cache.size(1)) must be a power of two >= 32, got ",
+              page, " for k_cache ", k_cache.sizes());
+  TORCH_CHECK(page_table.is_cuda() && page_table.device() == q.device() &&
+                  page_table.scalar_type() == at::kInt &&
+                  page_table.is_contiguous() && page_table.dim() == 2 &&
+                  page_table.size(0) > 0 && page_table.size(1) > 0 &&
+                  page_table.size(1) * page < (1LL << 31), who,
+              ": page_table must be int32 [S,max_pages] contiguous on q's "
+              "GPU, got ", page_table.scalar_type(), " ", page_table.sizes(),
+              " on ", page_table.device());
+  check_i32_rows(lengths, q.device(), n, who, "lengths");
+  check_i32_rows(slots, q.device(), n, who, "slots");
+  const int64_t S = page_table.size(0), max_pages = page_table.size(1);
+  TORCH_CHECK(max_len >= 1 && max_len <= max_pages * page, who,
+              ": max_len must be in [1, max_pages * page], got ", max_len,
+              " for page_table ", page_table.sizes(), " and page ", page);
+  TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
+  TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
+  if (window >= max_len) window = 0;   // such a window cuts nothing off
+  const int64_t span = window > 0 ? std::min(max_len, window + 31) : max_len;
+  const int64_t chunk = decode_batched_split((int)n, (int)hkv, span, 0,
+                                             decode_paged_tile(), n_chunks);
+  int lg = 0;
+  while ((1LL << lg) < page) ++lg;
+  auto o = at::empty_like(q);
+  Tensor ws;
+  float* ws_ptr = nullptr;
+  if (n_chunks > 1) {
+    ws = at::empty({n * hq * n_chunks * (d + 2)},
+                   q.options().dtype(at::kFloat));
+    ws_ptr = ws.data_ptr<float>();
+  }
+  decode_attn_paged_launch(
+      bfp(q), k_cache.data_ptr(), v_cache.data_ptr(), ks, vs, fp8, bfp_mut(o),
+      ws_ptr, page_table.data_ptr<int>(), lengths.data_ptr<int>(),
+      slots.data_ptr<int>(), (int)n, (int)hq, (int)hkv, (int)S,
+      (int)max_pages, lg, (int)P, (int)max_len, (int)window, (int)chunk,
+      (int)n_chunks, (int)d, (float)scale, cur_stream());
+  return o;
+}
+
+// decode_attn_batched on bf16 pools [P,page,hkv,d] through a page table.
+Tensor decode_attn_paged(const Tensor& q, const Tensor& k_cache,
+                         const Tensor& v_cache, const Tensor& page_table,
+                         const Tensor& lengths, const Tensor& slots,
+                         int64_t max_len, double scale, int64_t window,
+                         int64_t n_chunks) {
+  const char* who = "decode_attn_paged";
+  decode_dims(q, k_cache, v_cache, who, false);
+  return decode_paged_run(q, k_cache, v_cache, nullptr, nullptr, false,
+                          page_table, lengths, slots, max_len, scale, window,
+                          n_chunks, who);
+}
+
+// decode_attn_batched_fp8 on e4m3 pools [P,page,hkv,d] through a page table.
+Tensor decode_attn_paged_fp8(const Tensor& q, const Tensor& k_cache,
+                             const Tensor& v_cache,
+                             const c10::optional<Tensor>& k_scale,
+                             const c10::optional<Tensor>& v_scale,
+                             const Tensor& page_table, const Tensor& lengths,
+                             const Tensor& slots, int64_t max_len,
+                             double scale, int64_t window, int64_t n_chunks) {
+  const char* who = "decode_attn_paged_fp8";
+  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
+              who, ": q must be bf16 [n,hq,d], contiguous on GPU, got ",
+              q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
+  check_fp8_caches(k_cache, v_cache, q.device(), q.size(2), who);
+  const int64_t hkv = k_cache.size(2);
+  const float* ks = fp8_scale_ptr(k_scale, q.device(), hkv, who, "k_scale");
+  const float* vs = fp8_scale_ptr(v_scale, q.device(), hkv, who, "v_scale");
+  return decode_paged_run(q, k_cache, v_cache, ks, vs, true, page_table,
+                          lengths, slots, max_len, scale, window, n_chunks,
+                          who);
+}
+
 Tensor mfma_probe(const Tensor& A, const Tensor& B, bool alt) {
   CHECK_GPU(A); CHECK_GPU(B);
   auto D = at::zeros({32, 32}, A.options().dtype(at::kFloat));
@@ -1403,6 +1504,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_graph", &decode_attn_graph);
   m.def("decode_attn_batched", &decode_attn_batched, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_batched_fp8", &decode_attn_batched_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_paged", &decode_attn_paged, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_paged_fp8", &decode_attn_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("kv_append_fp8", &kv_append_fp8, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("positions"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("mfma_probe", &mfma_probe);
   m.def("ce_max", &ce_max);

@@ -698,7 +698,8 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
                              slots: torch.Tensor = None, max_len: int = None,
                              softmax_scale=None, window=None,
                              k_scale: torch.Tensor = None,
-                             v_scale: torch.Tensor = None) -> torch.Tensor:
+                             v_scale: torch.Tensor = None,
+                             page_table: torch.Tensor = None) -> torch.Tensor:
     """Decode attention for a batch of rows with their own lengths and cache
     rows (continuous-batching serving).
 
@@ -719,10 +720,22 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
     float8_e4m3fn caches (decode_attn_fp8.hip) hold real = stored * scale[h]
     with k_scale / v_scale fp32 [hkv] (None: ones); q and the result stay
     bf16.  The scales are ignored for caches of any other dtype.
+
+    page_table: int32 [S, max_pages] on the device makes the caches pools
+    [P, page, hkv, d] of either dtype (decode_attn_paged.hip), page a power
+    of two >= 32: slots[i] is a row of the table and position p of row i is
+    pool[page_table[slots[i], p // page], p % page].  max_len (None:
+    max_pages * page) must lie within the table.  A table entry outside
+    [0, P) contributes nothing: its positions are skipped and a row without
+    a valid attended page gives zeros.  The table is read on the device, so
+    it too may change in place under a captured graph; the torch path reads
+    it on the host and gathers each row's pages.
     """
     n, hq, d = q.shape
     S, max_s, hkv = k_cache.shape[:3]
     scale = softmax_scale if softmax_scale is not None else d ** -0.5
+    if page_table is not None:
+        S, max_s = page_table.shape[0], page_table.shape[1] * max_s
     max_len = max_s if max_len is None else int(max_len)
     if slots is None:
         assert n == S, "slots=None needs one q row per cache row"
@@ -730,6 +743,15 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
     fp8 = k_cache.dtype == torch.float8_e4m3fn
     if q.is_cuda and native_available() and q.dtype == torch.bfloat16 \
             and d in (64, 128) and hq // hkv <= 16:
+        if page_table is not None:
+            if fp8:
+                return get_ext().decode_attn_paged_fp8(
+                    q.contiguous(), k_cache, v_cache, k_scale, v_scale,
+                    page_table, lengths, slots, max_len, float(scale),
+                    int(window or 0), 0)
+            return get_ext().decode_attn_paged(
+                q.contiguous(), k_cache, v_cache, page_table, lengths, slots,
+                max_len, float(scale), int(window or 0), 0)
         if fp8:
             return get_ext().decode_attn_batched_fp8(
                 q.contiguous(), k_cache, v_cache, k_scale, v_scale, lengths,
@@ -737,12 +759,49 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
         return get_ext().decode_attn_batched(
             q.contiguous(), k_cache, v_cache, lengths, slots, max_len,
             float(scale), int(window or 0), 0)
+    if page_table is not None:
+        return _decode_attention_paged_torch(
+            q, k_cache, v_cache, page_table, lengths, slots, max_len, scale,
+            window, k_scale, v_scale)
     if fp8:
         return _decode_attention_batched_fp8_torch(
             q, k_cache, v_cache, lengths, slots, max_len, scale, window,
             k_scale, v_scale)
     return _decode_attention_batched_torch(q, k_cache, v_cache, lengths,
                                            slots, max_len, scale, window)
+
+
+def _decode_attention_paged_torch(q, k_pool, v_pool, page_table, lengths,
+                                  slots, max_len, scale, window, k_scale=None,
+                                  v_scale=None):
+    """`decode_attention_batched` on a paged cache in torch: each row's valid
+    pages gathered into a contiguous row, positions of invalid pages left
+    out, then the contiguous torch path on that one row."""
+    P, page = k_pool.shape[:2]
+    S = page_table.shape[0]
+    table = page_table.tolist()
+    fp8 = k_pool.dtype == torch.float8_e4m3fn
+    one = torch.ones(1, dtype=torch.int32, device=q.device)
+    out = torch.zeros_like(q)
+    for i, (cur, s) in enumerate(zip(lengths.tolist(), slots.tolist())):
+        cur = min(cur, max_len)
+        if cur <= 0 or not 0 <= s < S:
+            continue
+        start = max(0, cur - window) if window else 0
+        pos = torch.arange(start, cur, device=q.device)
+        ids = torch.tensor(table[s], device=q.device)[pos // page]
+        keep = (ids >= 0) & (ids < P)
+        if not bool(keep.any()):
+            continue
+        ids, off = ids[keep], (pos % page)[keep]
+        k_row, v_row = k_pool[ids, off][None], v_pool[ids, off][None]
+        L = k_row.shape[1]
+        f = _decode_attention_batched_fp8_torch if fp8 \
+            else _decode_attention_batched_torch
+        extra = (k_scale, v_scale) if fp8 else ()
+        out[i:i + 1] = f(q[i:i + 1], k_row, v_row, L * one, 0 * one, L,
+                         scale, None, *extra)
+    return out
 
 
 def _decode_attention_batched_torch(q, k_cache, v_cache, lengths, slots,

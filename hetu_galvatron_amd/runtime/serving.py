@@ -19,6 +19,16 @@ float8_e4m3fn with static per-layer, per-head scales: new rows are quantised
 and scattered by one `kv_cache_append` per layer, decode attends to the
 bytes directly, and prefill attends to its fresh bf16 K/V through flash and
 writes the slot's rows through the same op.
+
+`page_size=N` (batched attention only, either cache dtype) replaces the
+per-slot rows by one pool of `num_pages` pages of N positions per layer.  A
+request reserves ceil((prompt + max_new_tokens) / N) pages at admission and
+is refused when the pool cannot cover them; pages are assigned lazily, the
+prompt's at prefill and one more whenever a slot's length crosses a page
+boundary, and all return to the free list at release.  A persistent device
+table [max_slots, max_seq / N] maps (slot, page index) to a pool page; cache
+writes go to (page id, offset) and decode passes the table to
+`decode_attention_batched`.
 """
 from __future__ import annotations
 
@@ -54,16 +64,32 @@ class ContinuousBatchingEngine:
 
     def __init__(self, model, max_slots: int = 8, max_seq: int = 4096,
                  batched_attention: bool = False, kv_cache_dtype: str = None,
-                 kv_scales: torch.Tensor = None):
+                 kv_scales: torch.Tensor = None, page_size: int = None,
+                 num_pages: int = None):
         """kv_cache_dtype: None (the model's dtype) or "fp8"; kv_scales:
         fp32 [n_layers, 2, hkv] dequantisation scales of the fp8 cache
-        (k, v per layer; None: ones)."""
+        (k, v per layer; None: ones).  page_size: None (one contiguous row
+        per slot) or the positions per page of a paged cache, a power of two
+        >= 32 that divides max_seq; num_pages: pages in the pool (None:
+        max_slots * max_seq / page_size, the contiguous cache's memory)."""
         if kv_cache_dtype not in (None, "fp8"):
             raise ValueError(f"kv_cache_dtype must be None or 'fp8', got "
                              f"{kv_cache_dtype!r}")
         if kv_cache_dtype == "fp8" and not batched_attention:
             raise ValueError("kv_cache_dtype='fp8' needs "
                              "batched_attention=True")
+        if page_size is None and num_pages is not None:
+            raise ValueError("num_pages needs page_size")
+        if page_size is not None:
+            if not batched_attention:
+                raise ValueError("page_size needs batched_attention=True")
+            if page_size < 32 or page_size & (page_size - 1) \
+                    or max_seq % page_size:
+                raise ValueError(f"page_size must be a power of two >= 32 "
+                                 f"that divides max_seq, got {page_size}")
+            if num_pages is None:
+                num_pages = max_slots * max_seq // page_size
+        self.page_size = page_size
         self.batched_attention = batched_attention
         self.gen = GalvatronGenerator(model, max_batch=max_slots,
                                       max_seq=max_seq)
@@ -73,9 +99,21 @@ class ContinuousBatchingEngine:
         self.max_seq = max_seq
         dtype = torch.float8_e4m3fn if kv_cache_dtype == "fp8" \
             else next(self.gen.embedding.parameters()).dtype
-        self.cache = KVCache(len(self.gen.layers), max_slots, max_seq,
-                             m.kv_heads, m.head_dim, self.gen._dev,
-                             dtype=dtype)
+        if page_size is None:
+            self.cache = KVCache(len(self.gen.layers), max_slots, max_seq,
+                                 m.kv_heads, m.head_dim, self.gen._dev,
+                                 dtype=dtype)
+        else:                                   # pools [num_pages, page, ..]
+            self.cache = KVCache(len(self.gen.layers), num_pages, page_size,
+                                 m.kv_heads, m.head_dim, self.gen._dev,
+                                 dtype=dtype)
+            self.free_pages: List[int] = list(range(num_pages))[::-1]
+            self.unreserved = num_pages
+            self.pages: Dict[int, List[int]] = {}   # slot -> owned pages
+            self.reserved: Dict[int, int] = {}      # slot -> pages reserved
+            self.page_table = torch.full(
+                (max_slots, max_seq // page_size), -1, dtype=torch.int32,
+                device=self.gen._dev)
         if kv_scales is not None:
             if not self.cache.fp8 or tuple(kv_scales.shape) != (
                     len(self.gen.layers), 2, m.kv_heads):
@@ -109,13 +147,28 @@ class ContinuousBatchingEngine:
         temperature > 0 samples with a per-request seeded generator."""
         assert self.free, "no free slots"
         assert prompt_ids.dim() == 1 and max_new_tokens >= 1
+        sp = prompt_ids.shape[0]
+        assert sp + max_new_tokens <= self.max_seq
+        if self.page_size is not None:
+            need = -(-(sp + max_new_tokens) // self.page_size)
+            if need > self.unreserved:
+                raise RuntimeError(
+                    f"KV page pool exhausted: the request needs {need} "
+                    f"pages, {self.unreserved} are unreserved "
+                    f"({need - self.unreserved} short)")
         slot = self.free.pop()
         rid = self._next_rid
         self._next_rid += 1
-        sp = prompt_ids.shape[0]
-        assert sp + max_new_tokens <= self.max_seq
-        # single-slot prefill on the slot's contiguous cache row
-        view = _SlotCache(self.cache, slot)
+        if self.page_size is not None:
+            self.unreserved -= need
+            self.reserved[slot] = need
+            self.pages[slot] = []
+            self._grow(slot, sp)
+            view = _PagedSlotCache(self.cache, self.pages[slot],
+                                   self.page_size)
+        else:
+            # single-slot prefill on the slot's contiguous cache row
+            view = _SlotCache(self.cache, slot)
         logits = self._prefill(prompt_ids.unsqueeze(0), view)
         if temperature > 0:
             g = torch.Generator(device="cpu").manual_seed(seed)
@@ -135,6 +188,17 @@ class ContinuousBatchingEngine:
                                        and first == eos_id):
             self.release(rid)
         return rid
+
+    def _grow(self, slot: int, length: int) -> None:
+        """Give `slot` the pages that `length` positions need (within its
+        reservation) and enter them in the device table."""
+        own = self.pages[slot]
+        first = len(own)
+        while len(own) * self.page_size < length:
+            own.append(self.free_pages.pop())
+        if len(own) > first:
+            self.page_table[slot, first:len(own)] = torch.tensor(
+                own[first:], dtype=torch.int32, device=self.page_table.device)
 
     def _prefill(self, ids: torch.Tensor, view: "_SlotCache"):
         gen = self.gen
@@ -184,7 +248,19 @@ class ContinuousBatchingEngine:
         if self.batched_attention:
             slot_t = torch.tensor(active, device=dev)
             slot32 = slot_t.int()
-            pos32 = pos.int()
+            # where the new rows go: (cache row, position), or paged
+            # (page id, offset in the page)
+            wr_t, wr_pos = slot_t, pos
+            if self.page_size is not None:
+                for s in active:         # a length that crosses a boundary
+                    self._grow(s, self.lengths[s] + 1)
+                wr_t = torch.tensor(
+                    [self.pages[s][self.lengths[s] // self.page_size]
+                     for s in active], device=dev)
+                wr_pos = pos % self.page_size
+            wr32, wr_pos32 = wr_t.int(), wr_pos.int()
+            paged = {} if self.page_size is None \
+                else {"page_table": self.page_table}
             lengths_t = (pos + 1).int()      # the new token is attended too
             max_len = max(self.lengths[s] for s in active) + 1
         h = gen.embedding.word_embeddings(ids.transpose(0, 1))  # [1, n, hd]
@@ -205,16 +281,17 @@ class ContinuousBatchingEngine:
                 cache = self.cache
                 if cache.fp8:
                     kv_cache_append(k[0], v[0], cache.k[li], cache.v[li],
-                                    slot32, pos32, cache.k_scale[li],
+                                    wr32, wr_pos32, cache.k_scale[li],
                                     cache.v_scale[li])
                 else:
-                    cache.k[li][slot_t, pos] = k[0]
-                    cache.v[li][slot_t, pos] = v[0]
+                    cache.k[li][wr_t, wr_pos] = k[0]
+                    cache.v[li][wr_t, wr_pos] = v[0]
                 outs = [decode_attention_batched(
                     q[0], cache.k[li], cache.v[li], lengths_t,
                     slot32, max_len=max_len, softmax_scale=gen.scale,
                     window=getattr(gen, "window", None),
-                    k_scale=cache.k_scale[li], v_scale=cache.v_scale[li])]
+                    k_scale=cache.k_scale[li], v_scale=cache.v_scale[li],
+                    **paged)]
             else:
                 outs = self._attend_per_slot(li, active, q, k, v)
             o = torch.cat(outs, 0).unsqueeze(0).reshape(1, len(active), -1)
@@ -267,6 +344,10 @@ class ContinuousBatchingEngine:
         self.budgets.pop(slot, None)
         self.last_tok.pop(slot, None)
         self.lengths[slot] = 0
+        if self.page_size is not None:
+            self.free_pages.extend(self.pages.pop(slot))
+            self.unreserved += self.reserved.pop(slot)
+            self.page_table[slot].fill_(-1)
         self.free.append(slot)
 
     def collect(self, rid: int) -> List[int]:
@@ -298,3 +379,24 @@ class _SlotCache:
             return
         c.k[layer][self.slot, pos:pos + s] = k[0]
         c.v[layer][self.slot, pos:pos + s] = v[0]
+
+
+class _PagedSlotCache:
+    """KVCache adapter writing one slot's positions through its pages."""
+
+    def __init__(self, cache: KVCache, pages: List[int], page_size: int):
+        self.cache = cache
+        self.pages = pages
+        self.page_size = page_size
+
+    def write(self, layer: int, k, v, pos: int) -> None:
+        c = self.cache
+        p = torch.arange(pos, pos + k.shape[1], device=k.device)
+        ids = torch.tensor(self.pages, device=k.device)[p // self.page_size]
+        off = p % self.page_size
+        if c.fp8:
+            kv_cache_append(k[0], v[0], c.k[layer], c.v[layer], ids.int(),
+                            off.int(), c.k_scale[layer], c.v_scale[layer])
+            return
+        c.k[layer][ids, off] = k[0]
+        c.v[layer][ids, off] = v[0]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -330,6 +330,62 @@ def bench_decode_batched_fp8(iters, repeats=9):
               f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
 
 
+def bench_decode_paged(iters, repeats=9, contiguous_only=False):
+    """ops.decode_attention_batched on paged pools (pages of 32 and 128, ids
+    shuffled over the pool) beside the same call on the contiguous caches
+    holding the same rows, bf16 and e4m3: the cases, method and GB/s of
+    bench_decode_batched.  contiguous_only times only the contiguous rows (to
+    time a build of the extension that predates paging with the same code)."""
+    from hetu_galvatron_amd import ops
+    hq, hkv, d, max_s = 32, 8, 128, 4096
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in (8, 32):
+        q = torch.randn(n, hq, d, device="cuda", generator=g).bfloat16()
+        kc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        vc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        ks = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        vs = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        k8 = (kc.float() / ks[:, None]).to(torch.float8_e4m3fn)
+        v8 = (vc.float() / vs[:, None]).to(torch.float8_e4m3fn)
+        slots = torch.arange(n, dtype=torch.int32, device="cuda")
+        ladder = [max(1, round(max_s ** (i / (n - 1)))) for i in range(n)]
+        pools = {}
+        for page in () if contiguous_only else (32, 128):
+            P = n * max_s // page
+            perm = torch.randperm(P, device="cuda", generator=g)
+            inv = torch.empty_like(perm)
+            inv[perm] = torch.arange(P, device="cuda")
+            # pool page perm[j] holds page j of the caches' storage order
+            pools[page] = (perm.int().reshape(n, -1),) + tuple(
+                c.view(P, page, hkv, d)[inv].contiguous()
+                for c in (kc, vc, k8, v8))
+        for label, lens in (("uniform", [max_s] * n), ("mixed", ladder)):
+            lengths = torch.tensor(lens, dtype=torch.int32, device="cuda")
+            for name, width, k, v, sc in (
+                    ("bf16", 2, 1, 2, {}),
+                    ("fp8", 1, 3, 4, dict(k_scale=ks, v_scale=vs))):
+                gb = 2 * sum(lens) * hkv * d * width / 1e9
+                caches = (None, kc, vc, k8, v8)
+                rows = [("contiguous", lambda: ops.decode_attention_batched(
+                    q, caches[k], caches[v], lengths, slots,
+                    max_len=max(lens), **sc))]
+                for page, pl in pools.items():
+                    rows.append((f"page {page}", lambda pl=pl:
+                                 ops.decode_attention_batched(
+                                     q, pl[k], pl[v], lengths, slots,
+                                     max_len=max(lens), page_table=pl[0],
+                                     **sc)))
+                ref = rows[0][1]()
+                for what, fn in rows:
+                    assert torch.equal(fn(), ref), "paged != contiguous"
+                    t, lo, hi = median_of_windows(fn, iters, repeats)
+                    print(f"decode-paged n{n:<2d} {label:7s} {name:4s} "
+                          f"{what:10s} {t*1e6:8.1f} us "
+                          f"[{lo*1e6:.1f}, {hi*1e6:.1f}]  {gb/t:6.0f} GB/s")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -417,6 +473,8 @@ def main():
                     help="varlen entry: time only the dense kernels")
     ap.add_argument("--loop-only", action="store_true",
                     help="decode-batched entry: skip the batched op")
+    ap.add_argument("--contiguous-only", action="store_true",
+                    help="decode-paged entry: skip the paged pools")
     ap.add_argument("--composition-only", action="store_true",
                     help="qkv-varlen entry: time only the composition")
     args = ap.parse_args()
@@ -431,6 +489,8 @@ def main():
                it, args.repeats, args.loop_only),
            "decode-batched-fp8": lambda it: bench_decode_batched_fp8(
                it, args.repeats),
+           "decode-paged": lambda it: bench_decode_paged(
+               it, args.repeats, args.contiguous_only),
            "qkv-varlen": lambda it: bench_qkv_varlen(
                it, args.repeats, args.composition_only)}
     if args.what == "all":
