@@ -12,6 +12,7 @@
 #include <tuple>
 #include <vector>
 
+#include "decode_launch.h"
 #include "flash_attn_launch.h"
 
 // ---- launcher prototypes (defined in the sibling .hip TUs) ----------------
@@ -58,13 +59,6 @@ void qkv_grad_finish_launch(__bf16*, const __bf16*, const __bf16*, const float*,
 int multi_sumsq_grid(int);
 void multi_sumsq_launch(const long*, int, float*, hipStream_t);
 void decode_attn_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, int, int, int, int, int, int, int, float, const int*, hipStream_t);
-int decode_batched_tile();
-void decode_attn_batched_launch(const __bf16*, const __bf16*, const __bf16*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
-int decode_fp8_tile();
-void decode_attn_batched_fp8_launch(const __bf16*, const uint8_t*, const uint8_t*, const float*, const float*, __bf16*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
-int decode_paged_tile();
-void decode_attn_paged_launch(const __bf16*, const void*, const void*, const float*, const float*, bool, __bf16*, float*, const int*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
-void kv_append_fp8_launch(const __bf16*, const __bf16*, long, long, long, long, uint8_t*, uint8_t*, const float*, const float*, const int*, const int*, int, int, int, int, int, hipStream_t);
 
 namespace {
 
@@ -766,8 +760,7 @@ struct DecodeDims {
 };
 
 DecodeDims decode_dims(const Tensor& q, const Tensor& k_cache,
-                       const Tensor& v_cache, const char* who,
-                       bool same_rows = true) {
+                       const Tensor& v_cache, const char* who) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
               who, ": q must be bf16 [b,hq,d], contiguous on GPU, got ",
               q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
@@ -777,8 +770,7 @@ DecodeDims decode_dims(const Tensor& q, const Tensor& k_cache,
               k_cache.device(), " ", k_cache.sizes(), " strides ",
               k_cache.strides());
   TORCH_CHECK(is_bf16(k_cache) && k_cache.dim() == 4 &&
-                  (same_rows ? k_cache.size(0) == q.size(0)
-                             : k_cache.size(0) > 0) &&
+                  k_cache.size(0) == q.size(0) &&
                   k_cache.size(3) == q.size(2), who,
               ": k_cache must be bf16 [b,max_s,hkv,d] with q's batch and "
               "head dim, got ", k_cache.scalar_type(), " ", k_cache.sizes(),
@@ -872,103 +864,30 @@ Tensor decode_attn_graph(const Tensor& q, const Tensor& k_cache,
   return o;
 }
 
-// The split of the batched decode kernels: n_chunks = 0 asks for about 512
-// workgroups from the n*hkv rows with chunks of >= 256 positions; a positive
-// value is capped so that a chunk is at least one key tile.  -> chunk (a
-// multiple of tile); n_chunks becomes the count that a row can reach.
-int64_t decode_batched_split(int n, int hkv, int64_t max_len, int64_t window,
-                             int tile, int64_t& n_chunks) {
-  const int64_t span = window > 0 ? std::min(max_len, window) : max_len;
-  if (n_chunks == 0) {
-    n_chunks = std::max<int64_t>(1, 512 / ((int64_t)n * hkv));
-    n_chunks = std::min<int64_t>(n_chunks, (span + 255) / 256);
-  }
-  n_chunks = std::min<int64_t>(n_chunks, (span + tile - 1) / tile);
-  const int64_t chunk =
-      ((span + n_chunks - 1) / n_chunks + tile - 1) / tile * tile;
-  n_chunks = (span + chunk - 1) / chunk;   // drop chunks no row can reach
-  return chunk;
-}
-
-// Batched decode: row i of q [n,hq,d] attends to positions
-// [max(0, len_i - window), len_i) of row slots[i] of the caches
-// [S,max_s,hkv,d], len_i = min(lengths[i], max_len).  lengths and slots stay
-// on the device; launch geometry comes from the host arguments alone.
-// n_chunks = 0 chooses the split; a positive value is used as given, capped
-// so that a chunk is at least one key tile.
-Tensor decode_attn_batched(const Tensor& q, const Tensor& k_cache,
-                           const Tensor& v_cache, const Tensor& lengths,
-                           const Tensor& slots, int64_t max_len, double scale,
-                           int64_t window, int64_t n_chunks) {
-  const char* who = "decode_attn_batched";
-  const DecodeDims g = decode_dims(q, k_cache, v_cache, who, false);
-  const int n = g.b, hq = g.hq, d = g.d, max_s = g.max_s, hkv = g.hkv;
-  const int64_t S = k_cache.size(0);
-  TORCH_CHECK(n >= 1 && n <= 65535 && hkv <= 65535 && S < (1LL << 31), who,
-              ": n (rows of q) and hkv must be in [1, 65535] and the cache "
-              "rows below 2^31, got q ", q.sizes(), " k_cache ",
-              k_cache.sizes());
-  TORCH_CHECK(hq / hkv <= 16, who, ": qpg = hq / hkv must be <= 16, got hq ",
-              hq, " hkv ", hkv);
-  auto check_i32 = [&](const Tensor& t, const char* name) {
-    TORCH_CHECK(t.is_cuda() && t.device() == q.device() &&
-                    t.scalar_type() == at::kInt && t.is_contiguous() &&
-                    t.dim() == 1 && t.size(0) == n, who, ": ", name,
-                " must be int32 [n] contiguous on q's GPU (n = ", n,
-                "), got ", t.scalar_type(), " ", t.sizes(), " on ",
-                t.device());
-  };
-  check_i32(lengths, "lengths");
-  check_i32(slots, "slots");
-  TORCH_CHECK(max_len >= 1 && max_len <= max_s, who,
-              ": max_len must be in [1, max_s], got ", max_len,
-              " for k_cache ", k_cache.sizes());
-  TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
-  TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
-  if (window >= max_len) window = 0;   // such a window cuts nothing off
-  const int64_t chunk = decode_batched_split(n, hkv, max_len, window,
-                                             decode_batched_tile(), n_chunks);
-  auto o = at::empty_like(q);
-  Tensor ws;
-  float* ws_ptr = nullptr;
-  if (n_chunks > 1) {
-    ws = at::empty({(int64_t)n * hq * n_chunks * (d + 2)},
-                   q.options().dtype(at::kFloat));
-    ws_ptr = ws.data_ptr<float>();
-  }
-  decode_attn_batched_launch(bfp(q), bfp(k_cache), bfp(v_cache), bfp_mut(o),
-                             ws_ptr, lengths.data_ptr<int>(),
-                             slots.data_ptr<int>(), n, hq, hkv, (int)S, max_s,
-                             (int)max_len, (int)window, (int)chunk,
-                             (int)n_chunks, d, (float)scale, cur_stream());
-  return o;
-}
-
-// ---- FP8 (e4m3) KV cache ---------------------------------------------------
+// ---- batched decode: bf16 or FP8 (e4m3) caches, contiguous or paged --------
 bool is_e4m3(const Tensor& t) {
   return t.scalar_type() == at::kFloat8_e4m3fn;
 }
-const uint8_t* u8p(const Tensor& t) {
-  return static_cast<const uint8_t*>(t.data_ptr());
-}
 
-// caches: e4m3 [S, max_s, hkv, d] contiguous on `dev`, d 64 or 128
-void check_fp8_caches(const Tensor& k_cache, const Tensor& v_cache,
-                      c10::Device dev, int64_t d, const char* who) {
+// caches: `dtype` [S, max_s, hkv, d] (pools: [P, page, hkv, d]), contiguous
+// and 16-byte aligned on `dev`, d 64 or 128
+void check_kv_caches(const Tensor& k_cache, const Tensor& v_cache,
+                     at::ScalarType dtype, c10::Device dev, int64_t d,
+                     const char* who) {
   TORCH_CHECK(k_cache.is_cuda() && k_cache.device() == dev &&
-                  k_cache.is_contiguous() && is_e4m3(k_cache) &&
+                  k_cache.is_contiguous() && k_cache.scalar_type() == dtype &&
                   k_cache.dim() == 4 && k_cache.size(0) > 0 &&
                   k_cache.size(0) < (1LL << 31) && k_cache.size(3) == d &&
                   reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0,
-              who, ": k_cache must be float8_e4m3fn [S,max_s,hkv,d], "
+              who, ": k_cache must be ", dtype, " [S,max_s,hkv,d], "
               "contiguous and 16-byte aligned on ", dev, " with d = ", d,
               ", got ", k_cache.scalar_type(), " ", k_cache.sizes(), " on ",
               k_cache.device());
   TORCH_CHECK(v_cache.is_cuda() && v_cache.device() == dev &&
-                  v_cache.is_contiguous() && is_e4m3(v_cache) &&
+                  v_cache.is_contiguous() && v_cache.scalar_type() == dtype &&
                   v_cache.sizes() == k_cache.sizes() &&
                   reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
-              who, ": v_cache must be float8_e4m3fn, contiguous, 16-byte "
+              who, ": v_cache must be ", dtype, ", contiguous, 16-byte "
               "aligned and shaped like k_cache, got ", v_cache.scalar_type(),
               " ", v_cache.sizes(), " on ", v_cache.device());
   TORCH_CHECK(d == 64 || d == 128, who, ": head dim must be 64|128, got ", d);
@@ -996,22 +915,49 @@ void check_i32_rows(const Tensor& t, c10::Device dev, int64_t n,
               "), got ", t.scalar_type(), " ", t.sizes(), " on ", t.device());
 }
 
-// decode_attn_batched on e4m3 caches: real K = stored * k_scale[h], likewise
-// V; a missing scale is ones.  Same split and the same refusals.
-Tensor decode_attn_batched_fp8(const Tensor& q, const Tensor& k_cache,
-                               const Tensor& v_cache,
-                               const c10::optional<Tensor>& k_scale,
-                               const c10::optional<Tensor>& v_scale,
-                               const Tensor& lengths, const Tensor& slots,
-                               int64_t max_len, double scale, int64_t window,
-                               int64_t n_chunks) {
-  const char* who = "decode_attn_batched_fp8";
+// The split of the batched decode kernels over `span` positions: n_chunks = 0
+// asks for about 512 workgroups from the n*hkv rows with chunks of >= 256
+// positions; a positive value is capped so that a chunk is at least one key
+// tile.  -> chunk (a multiple of tile); n_chunks becomes the count that a row
+// can reach.
+int64_t decode_batched_split(int64_t n, int64_t hkv, int64_t span, int tile,
+                             int64_t& n_chunks) {
+  if (n_chunks == 0) {
+    n_chunks = std::max<int64_t>(1, 512 / (n * hkv));
+    n_chunks = std::min<int64_t>(n_chunks, (span + 255) / 256);
+  }
+  n_chunks = std::min<int64_t>(n_chunks, (span + tile - 1) / tile);
+  const int64_t chunk =
+      ((span + n_chunks - 1) / n_chunks + tile - 1) / tile * tile;
+  n_chunks = (span + chunk - 1) / chunk;   // drop chunks no row can reach
+  return chunk;
+}
+
+// What the four batched decode bindings share.  Row i of q [n,hq,d] attends
+// to positions [max(0, len_i - window), len_i), len_i = min(lengths[i],
+// max_len), of row slots[i] of the caches [S,max_s,hkv,d] or, with a
+// page_table [S,max_pages], of that table's row over the pools
+// [P,page,hkv,d]: position p at pool[page_table[slots[i], p / page],
+// p % page].  The caches are bf16, or e4m3 with real = stored * scale[h] and
+// a missing scale ones.  lengths, slots and the table stay on the device;
+// launch geometry comes from the host arguments alone.  n_chunks = 0 chooses
+// the split; a positive value is used as given, capped so that a chunk is at
+// least one key tile.  A paged row's tiles start on its first 32-key
+// boundary, so with a window the split covers window + 31 positions; without
+// one, chunks and tiles are those of the contiguous caches.
+Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
+                          const Tensor& v_cache, bool fp8,
+                          const c10::optional<Tensor>& k_scale,
+                          const c10::optional<Tensor>& v_scale,
+                          const Tensor* page_table, const Tensor& lengths,
+                          const Tensor& slots, int64_t max_len, double scale,
+                          int64_t window, int64_t n_chunks, const char* who) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
               who, ": q must be bf16 [n,hq,d], contiguous on GPU, got ",
               q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
   const int64_t n = q.size(0), hq = q.size(1), d = q.size(2);
-  check_fp8_caches(k_cache, v_cache, q.device(), d, who);
-  const int64_t S = k_cache.size(0), max_s = k_cache.size(1);
+  check_kv_caches(k_cache, v_cache, fp8 ? at::kFloat8_e4m3fn : at::kBFloat16,
+                  q.device(), d, who);
   const int64_t hkv = k_cache.size(2);
   TORCH_CHECK(n >= 1 && n <= 65535 && hkv >= 1 && hkv <= 65535 && hq > 0 &&
                   hq % hkv == 0, who, ": n and hkv must be in [1, 65535] and "
@@ -1019,33 +965,110 @@ Tensor decode_attn_batched_fp8(const Tensor& q, const Tensor& k_cache,
               k_cache.sizes());
   TORCH_CHECK(hq / hkv <= 16, who, ": qpg = hq / hkv must be <= 16, got hq ",
               hq, " hkv ", hkv);
-  const float* ks = fp8_scale_ptr(k_scale, q.device(), hkv, who, "k_scale");
-  const float* vs = fp8_scale_ptr(v_scale, q.device(), hkv, who, "v_scale");
+  DecodeBatchedArgs a{};
+  a.fp8 = fp8;
+  if (fp8) {
+    a.k_scale = fp8_scale_ptr(k_scale, q.device(), hkv, who, "k_scale");
+    a.v_scale = fp8_scale_ptr(v_scale, q.device(), hkv, who, "v_scale");
+  }
+  int64_t max_pos = k_cache.size(1);       // positions a row can hold
+  if (page_table) {
+    const Tensor& t = *page_table;
+    const int64_t page = k_cache.size(1);
+    TORCH_CHECK(page >= 32 && (page & (page - 1)) == 0, who,
+                ": page (k_cache.size(1)) must be a power of two >= 32, got ",
+                page, " for k_cache ", k_cache.sizes());
+    TORCH_CHECK(t.is_cuda() && t.device() == q.device() &&
+                    t.scalar_type() == at::kInt && t.is_contiguous() &&
+                    t.dim() == 2 && t.size(0) > 0 && t.size(1) > 0 &&
+                    t.size(1) * page < (1LL << 31), who,
+                ": page_table must be int32 [S,max_pages] contiguous on q's "
+                "GPU, got ", t.scalar_type(), " ", t.sizes(), " on ",
+                t.device());
+    a.table = t.data_ptr<int>();
+    a.S = (int)t.size(0);
+    a.max_pages = (int)t.size(1);
+    a.P = (int)k_cache.size(0);
+    while ((1LL << a.lg) < page) ++a.lg;
+    max_pos = t.size(1) * page;
+  } else {
+    a.S = (int)k_cache.size(0);
+    a.max_s = (int)k_cache.size(1);
+  }
   check_i32_rows(lengths, q.device(), n, who, "lengths");
   check_i32_rows(slots, q.device(), n, who, "slots");
-  TORCH_CHECK(max_len >= 1 && max_len <= max_s, who,
-              ": max_len must be in [1, max_s], got ", max_len,
+  TORCH_CHECK(max_len >= 1 && max_len <= max_pos, who,
+              ": max_len must be in [1, ", max_pos, "] (the positions of a "
+              "cache row or of a table row's pages), got ", max_len,
               " for k_cache ", k_cache.sizes());
   TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
   TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
   if (window >= max_len) window = 0;   // such a window cuts nothing off
-  const int64_t chunk = decode_batched_split((int)n, (int)hkv, max_len,
-                                             window, decode_fp8_tile(),
-                                             n_chunks);
+  const int64_t span =
+      window > 0 ? std::min(max_len, window + (page_table ? 31 : 0)) : max_len;
+  const int64_t chunk =
+      decode_batched_split(n, hkv, span, decode_batched_tile(), n_chunks);
   auto o = at::empty_like(q);
   Tensor ws;
-  float* ws_ptr = nullptr;
   if (n_chunks > 1) {
     ws = at::empty({n * hq * n_chunks * (d + 2)},
                    q.options().dtype(at::kFloat));
-    ws_ptr = ws.data_ptr<float>();
+    a.part = ws.data_ptr<float>();
   }
-  decode_attn_batched_fp8_launch(
-      bfp(q), u8p(k_cache), u8p(v_cache), ks, vs, bfp_mut(o), ws_ptr,
-      lengths.data_ptr<int>(), slots.data_ptr<int>(), (int)n, (int)hq,
-      (int)hkv, (int)S, (int)max_s, (int)max_len, (int)window, (int)chunk,
-      (int)n_chunks, (int)d, (float)scale, cur_stream());
+  a.q = bfp(q);
+  a.k_cache = k_cache.data_ptr();
+  a.v_cache = v_cache.data_ptr();
+  a.lengths = lengths.data_ptr<int>();
+  a.slots = slots.data_ptr<int>();
+  a.o = bfp_mut(o);
+  a.n = (int)n; a.hq = (int)hq; a.hkv = (int)hkv; a.d = (int)d;
+  a.max_len = (int)max_len; a.window = (int)window; a.chunk = (int)chunk;
+  a.n_chunks = (int)n_chunks; a.scale = (float)scale;
+  decode_batched_launch(a, cur_stream());
   return o;
+}
+
+Tensor decode_attn_batched(const Tensor& q, const Tensor& k_cache,
+                           const Tensor& v_cache, const Tensor& lengths,
+                           const Tensor& slots, int64_t max_len, double scale,
+                           int64_t window, int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, false, {}, {}, nullptr,
+                            lengths, slots, max_len, scale, window, n_chunks,
+                            "decode_attn_batched");
+}
+
+Tensor decode_attn_batched_fp8(const Tensor& q, const Tensor& k_cache,
+                               const Tensor& v_cache,
+                               const c10::optional<Tensor>& k_scale,
+                               const c10::optional<Tensor>& v_scale,
+                               const Tensor& lengths, const Tensor& slots,
+                               int64_t max_len, double scale, int64_t window,
+                               int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
+                            nullptr, lengths, slots, max_len, scale, window,
+                            n_chunks, "decode_attn_batched_fp8");
+}
+
+Tensor decode_attn_paged(const Tensor& q, const Tensor& k_cache,
+                         const Tensor& v_cache, const Tensor& page_table,
+                         const Tensor& lengths, const Tensor& slots,
+                         int64_t max_len, double scale, int64_t window,
+                         int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, false, {}, {}, &page_table,
+                            lengths, slots, max_len, scale, window, n_chunks,
+                            "decode_attn_paged");
+}
+
+Tensor decode_attn_paged_fp8(const Tensor& q, const Tensor& k_cache,
+                             const Tensor& v_cache,
+                             const c10::optional<Tensor>& k_scale,
+                             const c10::optional<Tensor>& v_scale,
+                             const Tensor& page_table, const Tensor& lengths,
+                             const Tensor& slots, int64_t max_len,
+                             double scale, int64_t window, int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
+                            &page_table, lengths, slots, max_len, scale,
+                            window, n_chunks, "decode_attn_paged_fp8");
 }
 
 // Quantise k, v [n,hkv,d] bf16 (any row and head stride that keeps 16-byte
@@ -1074,7 +1097,7 @@ void kv_append_fp8(const Tensor& k, const Tensor& v, Tensor& k_cache,
               ": v must be shaped like k on k's GPU, got ", v.sizes(),
               " for k ", k.sizes());
   const int64_t n = k.size(0), hkv = k.size(1), d = k.size(2);
-  check_fp8_caches(k_cache, v_cache, k.device(), d, who);
+  check_kv_caches(k_cache, v_cache, at::kFloat8_e4m3fn, k.device(), d, who);
   TORCH_CHECK(k_cache.size(2) == hkv && n <= 65535, who,
               ": the caches must have k's hkv (", hkv, ") and n <= 65535, "
               "got k_cache ", k_cache.sizes(), " for k ", k.sizes());
@@ -1089,105 +1112,6 @@ void kv_append_fp8(const Tensor& k, const Tensor& v, Tensor& k_cache,
       static_cast<uint8_t*>(v_cache.data_ptr()), ks, vs,
       slots.data_ptr<int>(), positions.data_ptr<int>(), (int)n, (int)hkv,
       (int)d, (int)k_cache.size(0), (int)k_cache.size(1), cur_stream());
-}
-
-// ---- paged KV cache --------------------------------------------------------
-// What the two paged bindings share once q and the pools [P,page,hkv,d] are
-// checked: row i attends to [max(0, len_i - window), len_i) of table row
-// slots[i], position p at pool[page_table[slots[i], p / page], p % page].
-// The split is decode_batched_split on the row's tiles from its first 32-key
-// boundary: window + 31 positions with a window, max_len without (then
-// chunks and tiles are those of the contiguous bindings).
-Tensor decode_paged_run(const Tensor& q, const Tensor& k_cache,
-                        const Tensor& v_cache, const float* ks,
-                        const float* vs, bool fp8, const Tensor& page_table,
-                        const Tensor& lengths, const Tensor& slots,
-                        int64_t max_len, double scale, int64_t window,
-                        int64_t n_chunks, const char* who) {
-  const int64_t n = q.size(0), hq = q.size(1), d = q.size(2);
-  const int64_t P = k_cache.size(0), page = k_cache.size(1);
-  const int64_t hkv = k_cache.size(2);
-  TORCH_CHECK(n >= 1 && n <= 65535 && hkv >= 1 && hkv <= 65535 && hq > 0 &&
-                  hq % hkv == 0 && P < (1LL << 31), who,
-              ": n and hkv must be in [1, 65535], hq % hkv == 0 and the pool "
-              "below 2^31 pages, got q ", q.sizes(), " k_cache ",
-              k_cache.sizes());
-  TORCH_CHECK(hq / hkv <= 16, who, ": qpg = hq / hkv must be <= 16, got hq ",
-              hq, " hkv ", hkv);
-  TORCH_CHECK(page >= 32 && (page & (page - 1)) == 0, who,
-              ": page (k_cache.size(1)) must be a power of two >= 32, got ",
-              page, " for k_cache ", k_cache.sizes());
-  TORCH_CHECK(page_table.is_cuda() && page_table.device() == q.device() &&
-                  page_table.scalar_type() == at::kInt &&
-                  page_table.is_contiguous() && page_table.dim() == 2 &&
-                  page_table.size(0) > 0 && page_table.size(1) > 0 &&
-                  page_table.size(1) * page < (1LL << 31), who,
-              ": page_table must be int32 [S,max_pages] contiguous on q's "
-              "GPU, got ", page_table.scalar_type(), " ", page_table.sizes(),
-              " on ", page_table.device());
-  check_i32_rows(lengths, q.device(), n, who, "lengths");
-  check_i32_rows(slots, q.device(), n, who, "slots");
-  const int64_t S = page_table.size(0), max_pages = page_table.size(1);
-  TORCH_CHECK(max_len >= 1 && max_len <= max_pages * page, who,
-              ": max_len must be in [1, max_pages * page], got ", max_len,
-              " for page_table ", page_table.sizes(), " and page ", page);
-  TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
-  TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
-  if (window >= max_len) window = 0;   // such a window cuts nothing off
-  const int64_t span = window > 0 ? std::min(max_len, window + 31) : max_len;
-  const int64_t chunk = decode_batched_split((int)n, (int)hkv, span, 0,
-                                             decode_paged_tile(), n_chunks);
-  int lg = 0;
-  while ((1LL << lg) < page) ++lg;
-  auto o = at::empty_like(q);
-  Tensor ws;
-  float* ws_ptr = nullptr;
-  if (n_chunks > 1) {
-    ws = at::empty({n * hq * n_chunks * (d + 2)},
-                   q.options().dtype(at::kFloat));
-    ws_ptr = ws.data_ptr<float>();
-  }
-  decode_attn_paged_launch(
-      bfp(q), k_cache.data_ptr(), v_cache.data_ptr(), ks, vs, fp8, bfp_mut(o),
-      ws_ptr, page_table.data_ptr<int>(), lengths.data_ptr<int>(),
-      slots.data_ptr<int>(), (int)n, (int)hq, (int)hkv, (int)S,
-      (int)max_pages, lg, (int)P, (int)max_len, (int)window, (int)chunk,
-      (int)n_chunks, (int)d, (float)scale, cur_stream());
-  return o;
-}
-
-// decode_attn_batched on bf16 pools [P,page,hkv,d] through a page table.
-Tensor decode_attn_paged(const Tensor& q, const Tensor& k_cache,
-                         const Tensor& v_cache, const Tensor& page_table,
-                         const Tensor& lengths, const Tensor& slots,
-                         int64_t max_len, double scale, int64_t window,
-                         int64_t n_chunks) {
-  const char* who = "decode_attn_paged";
-  decode_dims(q, k_cache, v_cache, who, false);
-  return decode_paged_run(q, k_cache, v_cache, nullptr, nullptr, false,
-                          page_table, lengths, slots, max_len, scale, window,
-                          n_chunks, who);
-}
-
-// decode_attn_batched_fp8 on e4m3 pools [P,page,hkv,d] through a page table.
-Tensor decode_attn_paged_fp8(const Tensor& q, const Tensor& k_cache,
-                             const Tensor& v_cache,
-                             const c10::optional<Tensor>& k_scale,
-                             const c10::optional<Tensor>& v_scale,
-                             const Tensor& page_table, const Tensor& lengths,
-                             const Tensor& slots, int64_t max_len,
-                             double scale, int64_t window, int64_t n_chunks) {
-  const char* who = "decode_attn_paged_fp8";
-  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
-              who, ": q must be bf16 [n,hq,d], contiguous on GPU, got ",
-              q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
-  check_fp8_caches(k_cache, v_cache, q.device(), q.size(2), who);
-  const int64_t hkv = k_cache.size(2);
-  const float* ks = fp8_scale_ptr(k_scale, q.device(), hkv, who, "k_scale");
-  const float* vs = fp8_scale_ptr(v_scale, q.device(), hkv, who, "v_scale");
-  return decode_paged_run(q, k_cache, v_cache, ks, vs, true, page_table,
-                          lengths, slots, max_len, scale, window, n_chunks,
-                          who);
 }
 
 Tensor mfma_probe(const Tensor& A, const Tensor& B, bool alt) {

@@ -1,5 +1,6 @@
-// Row table and wave fence shared by the batched decode attention modules
-// (decode_attn_batched.hip: bf16 caches, decode_attn_fp8.hip: e4m3 caches).
+// Row table, addressing tags and wave fence of batched decode attention: the
+// chunk body and the merge kernel (decode_body.h), instantiated by
+// decode_attn_batched.hip for bf16 and e4m3 caches, contiguous and paged.
 #pragma once
 
 #include "common.h"
@@ -22,9 +23,9 @@ DEV_INLINE DbRow db_row(const int* __restrict__ lengths,
   return r;
 }
 
-// Where a row's keys live: the addressing tag of the chunk bodies
-// (decode_batched_body.h, decode_fp8_body.h).  The kernel fills in what it
-// was launched with; the body binds the tag to its row's slot.  Contiguous:
+// Where a row's keys live: the addressing tag of the chunk body
+// (decode_body.h).  The kernel fills in what it was launched with; the body
+// binds the tag to its row's slot.  Contiguous:
 // one cache row of max_s positions, base() is the element offset of
 // (slot, position 0, head hk).
 struct DbContig {

@@ -717,12 +717,12 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
     outside [0, S) gives zeros.  Elsewhere a loop over rows through the torch
     arithmetic of `decode_attention` (reads lengths and slots on the host).
 
-    float8_e4m3fn caches (decode_attn_fp8.hip) hold real = stored * scale[h]
-    with k_scale / v_scale fp32 [hkv] (None: ones); q and the result stay
-    bf16.  The scales are ignored for caches of any other dtype.
+    float8_e4m3fn caches (format tag DbE4m3 of decode_body.h) hold real =
+    stored * scale[h] with k_scale / v_scale fp32 [hkv] (None: ones); q and
+    the result stay bf16.  The scales are ignored for caches of any other dtype.
 
     page_table: int32 [S, max_pages] on the device makes the caches pools
-    [P, page, hkv, d] of either dtype (decode_attn_paged.hip), page a power
+    [P, page, hkv, d] of either dtype (addressing tag DbPaged), page a power
     of two >= 32: slots[i] is a row of the table and position p of row i is
     pool[page_table[slots[i], p // page], p % page].  max_len (None:
     max_pages * page) must lie within the table.  A table entry outside
