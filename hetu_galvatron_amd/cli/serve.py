@@ -2,13 +2,19 @@
 
   python -m hetu_galvatron_amd.cli.serve model.model_name=llama-3-8b \\
       ckpt.load=/path/to/ckpt serve.port=8000 serve.max_slots=8 \\
-      [--kv-cache-dtype fp8] [--page-size 128 [--num-pages 2048]]
+      [--kv-cache-dtype fp8] [--page-size 128 [--num-pages 2048]] \\
+      [--speculative-tokens 4]
 
 --kv-cache-dtype fp8 (or serve.kv_cache_dtype=fp8) keeps the KV cache in
 float8_e4m3fn and selects the batched decode attention it needs.
 --page-size N (or serve.page_size=N) pages the KV cache: a pool of
 --num-pages pages of N positions (default: max_slots * max_seq / N) shared
 by all slots; it selects batched attention too.
+--speculative-tokens K (or serve.speculative_tokens=K) verifies up to K
+prompt-lookup drafts per request and decode step (greedy requests only; the
+tokens are those of plain decoding); it selects batched attention too.  The
+decode loop reads finished requests from the engine's outputs, so it serves
+both return shapes of `step()`.
 
 POST /generate  {"prompt_ids": [..], "max_new_tokens": 64}
     -> {"request_id": r, "tokens": [...]}   (blocks until complete)
@@ -86,16 +92,18 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     opts = {"port": 8000, "host": "0.0.0.0", "max_slots": 8,
             "max_seq": 4096, "kv_cache_dtype": "", "page_size": 0,
-            "num_pages": 0}
+            "num_pages": 0, "speculative_tokens": 0}
     rest = []
     for i, a in enumerate(argv):
         if a == "--kv-cache-dtype" and i + 1 < len(argv):
             argv[i + 1] = "serve.kv_cache_dtype=" + argv[i + 1]
         elif a.startswith("--kv-cache-dtype="):
             opts["kv_cache_dtype"] = a.split("=", 1)[1]
-        elif a in ("--page-size", "--num-pages") and i + 1 < len(argv):
+        elif a in ("--page-size", "--num-pages", "--speculative-tokens") \
+                and i + 1 < len(argv):
             argv[i + 1] = f"serve.{a[2:].replace('-', '_')}={argv[i + 1]}"
-        elif a.startswith(("--page-size=", "--num-pages=")):
+        elif a.startswith(("--page-size=", "--num-pages=",
+                           "--speculative-tokens=")):
             k, v = a[2:].split("=", 1)
             opts[k.replace("-", "_")] = int(v)
         elif a.startswith("serve.") and "=" in a:
@@ -126,7 +134,10 @@ def main(argv=None):
     engine = ContinuousBatchingEngine(model, max_slots=opts["max_slots"],
                                       max_seq=opts["max_seq"],
                                       batched_attention=kv_dtype == "fp8"
-                                      or opts["page_size"] > 0,
+                                      or opts["page_size"] > 0
+                                      or opts["speculative_tokens"] > 0,
+                                      speculative_tokens=opts[
+                                          "speculative_tokens"],
                                       kv_cache_dtype=kv_dtype,
                                       page_size=opts["page_size"] or None,
                                       num_pages=opts["num_pages"] or None)

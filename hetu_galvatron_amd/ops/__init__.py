@@ -4,6 +4,7 @@ from .functional import (  # noqa: F401
     fused_add_rms_norm, flash_attention_varlen, fused_qkv_attention,
     fused_qkv_attention_varlen,
     flash_attention_fwd_only, flash_attention_bwd_only, flash_bias_attention,
-    decode_attention, decode_attention_batched, kv_cache_append,
+    decode_attention, decode_attention_batched, decode_attention_multi,
+    kv_cache_append,
 )
 from . import reference_ops  # noqa: F401

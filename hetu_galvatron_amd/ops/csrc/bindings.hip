@@ -945,17 +945,35 @@ int64_t decode_batched_split(int64_t n, int64_t hkv, int64_t span, int tile,
 // least one key tile.  A paged row's tiles start on its first 32-key
 // boundary, so with a window the split covers window + 31 positions; without
 // one, chunks and tiles are those of the contiguous caches.
+//
+// With q_lens (the four multi-token bindings) q is [n,T,hq,d], T <= 16, and
+// q_lens int32 [n] on q's device counts each row's real tokens: token
+// t < q_lens[i] sits at lengths[i] - q_lens[i] + t and attends up to itself
+// through its own window; a length above max_len makes the row empty.  The
+// split then covers window + T - 1 positions and counts the workgroups of
+// every column group.
 Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
                           const Tensor& v_cache, bool fp8,
                           const c10::optional<Tensor>& k_scale,
                           const c10::optional<Tensor>& v_scale,
                           const Tensor* page_table, const Tensor& lengths,
                           const Tensor& slots, int64_t max_len, double scale,
-                          int64_t window, int64_t n_chunks, const char* who) {
-  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) && q.dim() == 3,
-              who, ": q must be bf16 [n,hq,d], contiguous on GPU, got ",
-              q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
-  const int64_t n = q.size(0), hq = q.size(1), d = q.size(2);
+                          int64_t window, int64_t n_chunks, const char* who,
+                          const Tensor* q_lens = nullptr) {
+  if (q_lens) {
+    TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) &&
+                    q.dim() == 4 && q.size(1) >= 1 && q.size(1) <= 16, who,
+                ": q must be bf16 [n,T,hq,d] with 1 <= T <= 16, contiguous "
+                "on GPU, got ", q.scalar_type(), " ", q.sizes(), " strides ",
+                q.strides());
+  } else {
+    TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) &&
+                    q.dim() == 3, who,
+                ": q must be bf16 [n,hq,d], contiguous on GPU, got ",
+                q.scalar_type(), " ", q.sizes(), " strides ", q.strides());
+  }
+  const int64_t n = q.size(0), T = q_lens ? q.size(1) : 1;
+  const int64_t hq = q.size(-2), d = q.size(-1);
   check_kv_caches(k_cache, v_cache, fp8 ? at::kFloat8_e4m3fn : at::kBFloat16,
                   q.device(), d, who);
   const int64_t hkv = k_cache.size(2);
@@ -997,6 +1015,7 @@ Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
   }
   check_i32_rows(lengths, q.device(), n, who, "lengths");
   check_i32_rows(slots, q.device(), n, who, "slots");
+  if (q_lens) check_i32_rows(*q_lens, q.device(), n, who, "q_lens");
   TORCH_CHECK(max_len >= 1 && max_len <= max_pos, who,
               ": max_len must be in [1, ", max_pos, "] (the positions of a "
               "cache row or of a table row's pages), got ", max_len,
@@ -1004,14 +1023,18 @@ Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
   TORCH_CHECK(window >= 0, who, ": window must be >= 0, got ", window);
   TORCH_CHECK(n_chunks >= 0, who, ": n_chunks must be >= 0, got ", n_chunks);
   if (window >= max_len) window = 0;   // such a window cuts nothing off
-  const int64_t span =
-      window > 0 ? std::min(max_len, window + (page_table ? 31 : 0)) : max_len;
-  const int64_t chunk =
-      decode_batched_split(n, hkv, span, decode_batched_tile(), n_chunks);
+  const int64_t span = window > 0
+      ? std::min(max_len, window + T - 1 + (page_table ? 31 : 0)) : max_len;
+  const int64_t groups =
+      q_lens ? decode_multi_groups((int)T, (int)hq, (int)hkv) : 1;
+  TORCH_CHECK(hkv * groups <= 65535, who, ": hkv times the column groups of "
+              "T * hq / hkv must be <= 65535, got q ", q.sizes());
+  const int64_t chunk = decode_batched_split(
+      n, hkv * groups, span, decode_batched_tile(), n_chunks);
   auto o = at::empty_like(q);
   Tensor ws;
   if (n_chunks > 1) {
-    ws = at::empty({n * hq * n_chunks * (d + 2)},
+    ws = at::empty({n * T * hq * n_chunks * (d + 2)},
                    q.options().dtype(at::kFloat));
     a.part = ws.data_ptr<float>();
   }
@@ -1024,7 +1047,13 @@ Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
   a.n = (int)n; a.hq = (int)hq; a.hkv = (int)hkv; a.d = (int)d;
   a.max_len = (int)max_len; a.window = (int)window; a.chunk = (int)chunk;
   a.n_chunks = (int)n_chunks; a.scale = (float)scale;
-  decode_batched_launch(a, cur_stream());
+  if (q_lens) {
+    a.q_lens = q_lens->data_ptr<int>();
+    a.T = (int)T;
+    decode_multi_launch(a, cur_stream());
+  } else {
+    decode_batched_launch(a, cur_stream());
+  }
   return o;
 }
 
@@ -1069,6 +1098,56 @@ Tensor decode_attn_paged_fp8(const Tensor& q, const Tensor& k_cache,
   return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
                             &page_table, lengths, slots, max_len, scale,
                             window, n_chunks, "decode_attn_paged_fp8");
+}
+
+// Multi-token decode: q [n,T,hq,d], q_lens int32 [n]; see decode_batched_run.
+Tensor decode_attn_multi(const Tensor& q, const Tensor& k_cache,
+                         const Tensor& v_cache, const Tensor& lengths,
+                         const Tensor& q_lens, const Tensor& slots,
+                         int64_t max_len, double scale, int64_t window,
+                         int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, false, {}, {}, nullptr,
+                            lengths, slots, max_len, scale, window, n_chunks,
+                            "decode_attn_multi", &q_lens);
+}
+
+Tensor decode_attn_multi_fp8(const Tensor& q, const Tensor& k_cache,
+                             const Tensor& v_cache,
+                             const c10::optional<Tensor>& k_scale,
+                             const c10::optional<Tensor>& v_scale,
+                             const Tensor& lengths, const Tensor& q_lens,
+                             const Tensor& slots, int64_t max_len,
+                             double scale, int64_t window, int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
+                            nullptr, lengths, slots, max_len, scale, window,
+                            n_chunks, "decode_attn_multi_fp8", &q_lens);
+}
+
+Tensor decode_attn_multi_paged(const Tensor& q, const Tensor& k_cache,
+                               const Tensor& v_cache,
+                               const Tensor& page_table,
+                               const Tensor& lengths, const Tensor& q_lens,
+                               const Tensor& slots, int64_t max_len,
+                               double scale, int64_t window,
+                               int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, false, {}, {}, &page_table,
+                            lengths, slots, max_len, scale, window, n_chunks,
+                            "decode_attn_multi_paged", &q_lens);
+}
+
+Tensor decode_attn_multi_paged_fp8(const Tensor& q, const Tensor& k_cache,
+                                   const Tensor& v_cache,
+                                   const c10::optional<Tensor>& k_scale,
+                                   const c10::optional<Tensor>& v_scale,
+                                   const Tensor& page_table,
+                                   const Tensor& lengths,
+                                   const Tensor& q_lens, const Tensor& slots,
+                                   int64_t max_len, double scale,
+                                   int64_t window, int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
+                            &page_table, lengths, slots, max_len, scale,
+                            window, n_chunks, "decode_attn_multi_paged_fp8",
+                            &q_lens);
 }
 
 // Quantise k, v [n,hkv,d] bf16 (any row and head stride that keeps 16-byte
@@ -1429,6 +1508,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_batched", &decode_attn_batched, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_batched_fp8", &decode_attn_batched_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_paged", &decode_attn_paged, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_multi", &decode_attn_multi, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_multi_fp8", &decode_attn_multi_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_multi_paged", &decode_attn_multi_paged, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_multi_paged_fp8", &decode_attn_multi_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_paged_fp8", &decode_attn_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("kv_append_fp8", &kv_append_fp8, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("positions"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("mfma_probe", &mfma_probe);

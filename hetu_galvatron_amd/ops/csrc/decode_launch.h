@@ -29,9 +29,11 @@ struct DecodeBatchedArgs {
   const int* table;
   const int* lengths;
   const int* slots;
+  const int* q_lens;         // multi-token only
   __bf16* o;
   float* part;
   int n, hq, hkv, d;
+  int T;                     // multi-token only: query tokens per row
   int S;
   int max_s;                 // contiguous only
   int max_pages, lg, P;      // paged only
@@ -41,6 +43,17 @@ struct DecodeBatchedArgs {
 
 int decode_batched_tile();
 void decode_batched_launch(const DecodeBatchedArgs& a, hipStream_t st);
+
+// The multi-token call (decode_attn_multi.hip): q and o are [n, T, hq, d],
+// T <= 16, and q_lens int32 [n] counts each row's real tokens.  Token
+// t < q_lens[i] sits at pos = lengths[i] - q_lens[i] + t and attends to
+// [max(0, pos + 1 - window), pos]; lengths[i] must lie in (0, max_len] or the
+// row is empty.  With a window the split covers window + T - 1 positions
+// (paged: + 31); part is [n*T*hq, n_chunks, d+2].  decode_multi_groups: the
+// workgroups per (row, kv head, chunk), one per 16 or 32 columns of the
+// T * hq / hkv.
+int decode_multi_groups(int T, int hq, int hkv);
+void decode_multi_launch(const DecodeBatchedArgs& a, hipStream_t st);
 
 // k, v: [n, hkv, d] bf16 with row and head strides in elements (multiples of
 // 8, 16-byte aligned bases) and a contiguous last dim; d is 64 or 128.

@@ -771,6 +771,100 @@ def decode_attention_batched(q: torch.Tensor, k_cache: torch.Tensor,
                                            slots, max_len, scale, window)
 
 
+@torch.no_grad()
+def decode_attention_multi(q: torch.Tensor, k_cache: torch.Tensor,
+                           v_cache: torch.Tensor, lengths: torch.Tensor,
+                           q_lens: torch.Tensor, slots: torch.Tensor,
+                           window=None, max_len: int = None,
+                           softmax_scale=None, n_chunks: int = None,
+                           k_scale: torch.Tensor = None,
+                           v_scale: torch.Tensor = None,
+                           page_table: torch.Tensor = None) -> torch.Tensor:
+    """Decode attention of up to T consecutive new tokens per row against
+    that row's cache, causal inside the block (speculative verification,
+    chunked decode).
+
+    q: [n, T, hq, d], 1 <= T <= 16 on the native path; caches, pools, scales,
+    slots, page_table, window and max_len as in `decode_attention_batched`.
+    lengths: int32 [n], the row's cached length with the new tokens included
+    (the caller has written them); q_lens: int32 [n] in [0, T], how many of
+    the T tokens are real.  Token t < q_lens[i] sits at pos = lengths[i] -
+    q_lens[i] + t and attends to [max(0, pos + 1 - window), pos] of cache row
+    (table row) slots[i].  o[i, t] is zeros for t >= q_lens[i] and for a row
+    with lengths[i] outside (0, max_len], q_lens[i] outside [0, T] or above
+    the length, or a slot outside [0, S).
+
+    Native CDNA4 kernel on GPU bf16 with d in (64, 128), hq/hkv <= 16 and
+    T <= 16 (decode_attn_multi.hip): the T * hq/hkv (token, head) columns of
+    a kv head share one pass over its K and V rows, 32 columns per workgroup.
+    Nothing is read back, so a captured graph replays after lengths, q_lens,
+    slots, the table and the caches change in place.  n_chunks (None: chosen)
+    forces the split-KV chunk count.  Elsewhere a loop over (row, token)
+    through the torch arithmetic of `decode_attention` at cur = pos + 1.
+    """
+    n, T, hq, d = q.shape
+    S, max_s, hkv = k_cache.shape[:3]
+    scale = softmax_scale if softmax_scale is not None else d ** -0.5
+    if page_table is not None:
+        S, max_s = page_table.shape[0], page_table.shape[1] * max_s
+    max_len = max_s if max_len is None else int(max_len)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if q.is_cuda and native_available() and q.dtype == torch.bfloat16 \
+            and d in (64, 128) and hq // hkv <= 16 and T <= 16:
+        ext = get_ext()
+        tail = (lengths, q_lens, slots, max_len, float(scale),
+                int(window or 0), int(n_chunks or 0))
+        sc = (k_scale, v_scale) if fp8 else ()
+        if page_table is not None:
+            f = ext.decode_attn_multi_paged_fp8 if fp8 \
+                else ext.decode_attn_multi_paged
+            return f(q.contiguous(), k_cache, v_cache, *sc, page_table, *tail)
+        f = ext.decode_attn_multi_fp8 if fp8 else ext.decode_attn_multi
+        return f(q.contiguous(), k_cache, v_cache, *sc, *tail)
+    return _decode_attention_multi_torch(
+        q, k_cache, v_cache, lengths, q_lens, slots, S, max_len, scale,
+        window, k_scale, v_scale, page_table)
+
+
+def _decode_attention_multi_torch(q, k_cache, v_cache, lengths, q_lens, slots,
+                                  S, max_len, scale, window, k_scale, v_scale,
+                                  page_table):
+    """Each (row, token) through `_decode_attention_torch` at cur = pos + 1
+    on the row's positions [0, cur): e4m3 rows dequantised, pages gathered,
+    positions of invalid pages left out."""
+    n, T = q.shape[:2]
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    ks = k_scale.float()[:, None] if fp8 and k_scale is not None else None
+    vs = v_scale.float()[:, None] if fp8 and v_scale is not None else None
+    P, page = k_cache.shape[:2]
+    out = torch.zeros_like(q)
+    for i, (L, ql, s) in enumerate(zip(lengths.tolist(), q_lens.tolist(),
+                                       slots.tolist())):
+        if not (0 < L <= max_len and 0 <= ql <= T and ql <= L
+                and 0 <= s < S):
+            continue
+        for t in range(ql):
+            cur = L - ql + t + 1
+            start = max(0, cur - window) if window else 0
+            if page_table is not None:
+                pos = torch.arange(start, cur, device=q.device)
+                ids = page_table[s].to(q.device)[pos // page]
+                keep = (ids >= 0) & (ids < P)
+                if not bool(keep.any()):
+                    continue
+                ids, off = ids[keep].long(), (pos % page)[keep]
+                k, v = k_cache[ids, off][None], v_cache[ids, off][None]
+            else:
+                k, v = k_cache[s:s + 1, start:cur], v_cache[s:s + 1, start:cur]
+            if fp8:
+                k, v = k.float(), v.float()
+                k = k if ks is None else k * ks
+                v = v if vs is None else v * vs
+            out[i, t] = _decode_attention_torch(
+                q[i, t][None], k, v, k.shape[1], scale, 0)[0]
+    return out
+
+
 def _decode_attention_paged_torch(q, k_pool, v_pool, page_table, lengths,
                                   slots, max_len, scale, window, k_scale=None,
                                   v_scale=None):

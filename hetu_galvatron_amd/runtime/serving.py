@@ -29,18 +29,40 @@ boundary, and all return to the free list at release.  A persistent device
 table [max_slots, max_seq / N] maps (slot, page index) to a pool page; cache
 writes go to (page id, offset) and decode passes the table to
 `decode_attention_batched`.
+
+`speculative_tokens=k` (batched attention only; every cache dtype, paged or
+not, with or without a sliding window) verifies up to k drafted tokens per
+slot and step: the pending token and the drafts run as T = 1 + drafts rows
+through the batched linears, their K/V go to the cache at their positions and
+one `decode_attention_multi` call per layer attends each of them causally.
+Greedy acceptance emits the model's own tokens while the drafts agree with
+them, so the output is that of plain greedy decoding in fewer steps.  Drafts
+come from prompt lookup (`ngram_draft`) or a `draft_fn`.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import torch
 
 from ..ops import (decode_attention, decode_attention_batched,
-                   flash_attention_fwd_only, kv_cache_append)
+                   decode_attention_multi, flash_attention_fwd_only,
+                   kv_cache_append)
 from .inference import GalvatronGenerator, KVCache
 
-__all__ = ["ContinuousBatchingEngine"]
+__all__ = ["ContinuousBatchingEngine", "ngram_draft"]
+
+
+def ngram_draft(history: List[int], k: int) -> List[int]:
+    """Prompt-lookup drafts: the up to k tokens that followed the latest
+    earlier occurrence of the history's last two tokens; [] without one."""
+    if k <= 0 or len(history) < 3:
+        return []
+    a, b = history[-2], history[-1]
+    for i in range(len(history) - 3, -1, -1):
+        if history[i] == a and history[i + 1] == b:
+            return history[i + 2:i + 2 + k]
+    return []
 
 
 def _rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
@@ -65,13 +87,27 @@ class ContinuousBatchingEngine:
     def __init__(self, model, max_slots: int = 8, max_seq: int = 4096,
                  batched_attention: bool = False, kv_cache_dtype: str = None,
                  kv_scales: torch.Tensor = None, page_size: int = None,
-                 num_pages: int = None):
+                 num_pages: int = None, speculative_tokens: int = 0,
+                 draft_fn: Callable[[List[int], int], List[int]] = None):
         """kv_cache_dtype: None (the model's dtype) or "fp8"; kv_scales:
         fp32 [n_layers, 2, hkv] dequantisation scales of the fp8 cache
         (k, v per layer; None: ones).  page_size: None (one contiguous row
         per slot) or the positions per page of a paged cache, a power of two
         >= 32 that divides max_seq; num_pages: pages in the pool (None:
-        max_slots * max_seq / page_size, the contiguous cache's memory)."""
+        max_slots * max_seq / page_size, the contiguous cache's memory).
+        speculative_tokens: drafts verified per slot and step (0: plain
+        decode; `step()` then returns one token per request, otherwise a
+        list); draft_fn(history, k) -> up to k proposed tokens replaces the
+        prompt-lookup drafter.  Slots that sample take no drafts."""
+        if speculative_tokens < 0:
+            raise ValueError("speculative_tokens must be >= 0")
+        if speculative_tokens and not batched_attention:
+            raise ValueError("speculative_tokens needs batched_attention=True")
+        self.speculative_tokens = speculative_tokens
+        self.draft_fn = draft_fn or ngram_draft
+        self.history: Dict[int, List[int]] = {}   # slot -> prompt + outputs
+        self.drafted: Dict[int, int] = {}         # request id -> drafts run
+        self.accepted: Dict[int, int] = {}        # request id -> drafts kept
         if kv_cache_dtype not in (None, "fp8"):
             raise ValueError(f"kv_cache_dtype must be None or 'fp8', got "
                              f"{kv_cache_dtype!r}")
@@ -178,6 +214,9 @@ class ContinuousBatchingEngine:
             self.samplers.pop(slot, None)
             first = int(logits.argmax(-1))
         self.outputs[rid] = [first]
+        if self.speculative_tokens:
+            self.history[slot] = prompt_ids.tolist() + [first]
+            self.drafted[rid] = self.accepted[rid] = 0
         self.slot_of[rid] = slot
         self.rid_of[slot] = rid
         self.lengths[slot] = sp
@@ -237,6 +276,8 @@ class ContinuousBatchingEngine:
         """One decode step for every active slot.  Returns {rid: token};
         requests whose budget hits zero are released after their token
         (their outputs stay readable in `self.outputs`)."""
+        if self.speculative_tokens:
+            return self._step_speculative()
         active = sorted(self.budgets)
         if not active:
             return {}
@@ -316,6 +357,108 @@ class ContinuousBatchingEngine:
                 self.release(rid)
         return out
 
+    def _step_speculative(self) -> Dict[int, List[int]]:
+        """One verification step: every active slot runs its pending token
+        and its drafts as rows (i, t), t < q_len_i <= T, of one batch."""
+        active = sorted(self.budgets)
+        if not active:
+            return {}
+        gen, dev, n = self.gen, self.gen._dev, len(active)
+        drafts = []
+        for s in active:
+            # emitting needs budget: a draft beyond budget - 1 cannot be used,
+            # and length + 1 + drafts stays inside the request's reservation
+            k = min(self.speculative_tokens, self.budgets[s] - 1)
+            d = [] if s in self.samplers or k <= 0 \
+                else [int(x) for x in self.draft_fn(self.history[s], k)][:k]
+            drafts.append(d)
+        T = 1 + max(len(d) for d in drafts)
+        q_lens = [1 + len(d) for d in drafts]
+        ids = torch.tensor([[self.last_tok[s]] + d + [0] * (T - 1 - len(d))
+                            for s, d in zip(active, drafts)], device=dev)
+        base = torch.tensor([self.lengths[s] for s in active], device=dev)
+        pos = (base[:, None] + torch.arange(T, device=dev)) \
+            .clamp_(max=self.max_seq - 1).reshape(-1)          # [n*T]
+        # rows (i, t) that are real, and where their K/V go
+        real = [(i, t) for i in range(n) for t in range(q_lens[i])]
+        real_t = torch.tensor([i * T + t for i, t in real], device=dev)
+        wr_pos = pos[real_t]
+        if self.page_size is None:
+            wr_t = torch.tensor([active[i] for i, _ in real], device=dev)
+        else:
+            for s, ql in zip(active, q_lens):
+                self._grow(s, self.lengths[s] + ql)
+            wr_t = torch.tensor(
+                [self.pages[active[i]][(self.lengths[active[i]] + t)
+                                       // self.page_size] for i, t in real],
+                device=dev)
+            wr_pos = wr_pos % self.page_size
+        wr32, wr_pos32 = wr_t.int(), wr_pos.int()
+        paged = {} if self.page_size is None \
+            else {"page_table": self.page_table}
+        q_lens_t = torch.tensor(q_lens, dtype=torch.int32, device=dev)
+        lengths_t = base.int() + q_lens_t      # the new tokens are attended
+        slot32 = torch.tensor(active, dtype=torch.int32, device=dev)
+        max_len = max(self.lengths[s] + ql for s, ql in zip(active, q_lens))
+        h = gen.embedding.word_embeddings(ids.reshape(1, -1).transpose(0, 1))
+        cache = self.cache
+        for li, layer in enumerate(gen.layers):
+            attn = layer.attention
+            residual = h
+            x = layer.input_norm(h)
+            q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
+            if getattr(attn, "q_layernorm", None) is not None:
+                q = attn.q_layernorm(q)
+                k = attn.k_layernorm(k)
+            if layer.rotary is not None:
+                cos_t, sin_t = layer.rotary.full_tables(self.max_seq, dev)
+                il = getattr(attn, "rope_interleaved", False)
+                q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
+                k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
+            if cache.fp8:
+                kv_cache_append(k[0][real_t], v[0][real_t], cache.k[li],
+                                cache.v[li], wr32, wr_pos32,
+                                cache.k_scale[li], cache.v_scale[li])
+            else:
+                cache.k[li][wr_t, wr_pos] = k[0][real_t]
+                cache.v[li][wr_t, wr_pos] = v[0][real_t]
+            o = decode_attention_multi(
+                q[0].reshape(n, T, *q.shape[2:]), cache.k[li], cache.v[li],
+                lengths_t, q_lens_t, slot32,
+                window=getattr(gen, "window", None), max_len=max_len,
+                softmax_scale=gen.scale, k_scale=cache.k_scale[li],
+                v_scale=cache.v_scale[li], **paged)
+            h = residual + attn.linear_proj(o.reshape(1, n * T, -1))
+            residual = h
+            h = residual + layer.mlp(layer.post_attn_norm(h))
+        h = gen.final_norm.norm(h)
+        logits = gen.lm_head.lm_head(h)[0].float()          # [n*T, V]
+        greedy = logits.argmax(-1).reshape(n, T).tolist()
+        out: Dict[int, List[int]] = {}
+        for i, (s, d) in enumerate(zip(active, drafts)):
+            rid, eos = self.rid_of[s], self.eos.get(s)
+            g = greedy[i]
+            if s in self.samplers:
+                g = [self._sample(logits[i * T], s)]
+            emitted = []
+            for j in range(len(d) + 1):      # g[j] follows the accepted j
+                emitted.append(g[j])
+                if len(emitted) == self.budgets[s] or g[j] == eos \
+                        or j == len(d) or d[j] != g[j]:
+                    break
+            out[rid] = emitted
+            self.outputs[rid].extend(emitted)
+            self.history[s].extend(emitted)
+            self.drafted[rid] += len(d)
+            self.accepted[rid] += len(emitted) - 1
+            # rejected positions stay above the length and are overwritten
+            self.lengths[s] += len(emitted)
+            self.last_tok[s] = emitted[-1]
+            self.budgets[s] -= len(emitted)
+            if self.budgets[s] == 0 or emitted[-1] == eos:
+                self.release(rid)
+        return out
+
     def _attend_per_slot(self, li, active, q, k, v):
         outs = []
         for i, s in enumerate(active):
@@ -343,6 +486,7 @@ class ContinuousBatchingEngine:
         self.rid_of.pop(slot, None)
         self.budgets.pop(slot, None)
         self.last_tok.pop(slot, None)
+        self.history.pop(slot, None)
         self.lengths[slot] = 0
         if self.page_size is not None:
             self.free_pages.extend(self.pages.pop(slot))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|decode-multi|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -386,6 +386,74 @@ def bench_decode_paged(iters, repeats=9, contiguous_only=False):
                           f"[{lo*1e6:.1f}, {hi*1e6:.1f}]  {gb/t:6.0f} GB/s")
 
 
+def bench_decode_multi(iters, repeats=9, expanded_only=False):
+    """ops.decode_attention_multi (T new tokens per row in one pass over the
+    row's K/V) beside what the one-token kernel does with the same work:
+    decode_attention_batched on the n*T expanded rows (q reshaped, lengths =
+    pos + 1, the slot repeated).  h32/8 d128, n in (8, 32), uniform 4096 and
+    the mixed ladder, T in (1, 2, 4, 8), bf16 and e4m3, contiguous and page
+    32.  expanded_only times only the expanded rows (to time a build of the
+    extension that predates the multi-token kernels with the same code)."""
+    from hetu_galvatron_amd import ops
+    hq, hkv, d, max_s, page = 32, 8, 128, 4096, 32
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in (8, 32):
+        kc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        vc = torch.randn(n, max_s, hkv, d, device="cuda",
+                         generator=g).bfloat16()
+        ks = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        vs = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        k8 = (kc.float() / ks[:, None]).to(torch.float8_e4m3fn)
+        v8 = (vc.float() / vs[:, None]).to(torch.float8_e4m3fn)
+        slots = torch.arange(n, dtype=torch.int32, device="cuda")
+        ladder = [max(1, round(max_s ** (i / (n - 1)))) for i in range(n)]
+        P = n * max_s // page
+        perm = torch.randperm(P, device="cuda", generator=g)
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(P, device="cuda")
+        table = perm.int().reshape(n, -1)
+        pool = [c.view(P, page, hkv, d)[inv].contiguous()
+                for c in (kc, vc, k8, v8)]
+        for T in (1, 2, 4, 8):
+            q = torch.randn(n, T, hq, d, device="cuda", generator=g).bfloat16()
+            q_lens = torch.full((n,), T, dtype=torch.int32, device="cuda")
+            steps = torch.arange(T, dtype=torch.int32, device="cuda")
+            for label, lens in (("uniform", [max_s] * n),
+                                ("mixed", [max(x, T) for x in ladder])):
+                lengths = torch.tensor(lens, dtype=torch.int32, device="cuda")
+                # the expanded rows: token t of row i attends to pos + 1 keys
+                lens_x = (lengths[:, None] - T + 1 + steps).reshape(-1)
+                slots_x = slots.repeat_interleave(T)
+                qx = q.reshape(n * T, hq, d)
+                for name, k, v, sc in (
+                        ("bf16", 0, 1, {}),
+                        ("fp8", 2, 3, dict(k_scale=ks, v_scale=vs))):
+                    for what, kk, vv, tb in (
+                            ("contiguous", (kc, vc, k8, v8)[k],
+                             (kc, vc, k8, v8)[v], {}),
+                            ("page 32", pool[k], pool[v],
+                             dict(page_table=table))):
+                        kw = dict(max_len=max(lens), **sc, **tb)
+                        rows = [("expanded", lambda: (
+                            ops.decode_attention_batched(
+                                qx, kk, vv, lens_x, slots_x, **kw)))]
+                        if not expanded_only:
+                            rows.append(("multi", lambda: (
+                                ops.decode_attention_multi(
+                                    q, kk, vv, lengths, q_lens, slots,
+                                    **kw))))
+                            err = (rows[1][1]().reshape(qx.shape).float()
+                                   - rows[0][1]().float()).abs().max()
+                            assert float(err) < 0.05, "multi != expanded"
+                        for how, fn in rows:
+                            t, lo, hi = median_of_windows(fn, iters, repeats)
+                            print(f"decode-multi n{n:<2d} T{T} {label:7s} "
+                                  f"{name:4s} {what:10s} {how:8s} "
+                                  f"{t*1e6:8.1f} us "
+                                  f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -475,6 +543,8 @@ def main():
                     help="decode-batched entry: skip the batched op")
     ap.add_argument("--contiguous-only", action="store_true",
                     help="decode-paged entry: skip the paged pools")
+    ap.add_argument("--expanded-only", action="store_true",
+                    help="decode-multi entry: time only the expanded rows")
     ap.add_argument("--composition-only", action="store_true",
                     help="qkv-varlen entry: time only the composition")
     args = ap.parse_args()
@@ -491,6 +561,8 @@ def main():
                it, args.repeats),
            "decode-paged": lambda it: bench_decode_paged(
                it, args.repeats, args.contiguous_only),
+           "decode-multi": lambda it: bench_decode_multi(
+               it, args.repeats, args.expanded_only),
            "qkv-varlen": lambda it: bench_qkv_varlen(
                it, args.repeats, args.composition_only)}
     if args.what == "all":
