@@ -952,6 +952,9 @@ int64_t decode_batched_split(int64_t n, int64_t hkv, int64_t span, int tile,
 // through its own window; a length above max_len makes the row empty.  The
 // split then covers window + T - 1 positions and counts the workgroups of
 // every column group.
+//
+// prefill (the four decode_attn_prefill* bindings): the multi-token call for
+// any T >= 1 on the prefill-shaped kernels, 128 columns per workgroup.
 Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
                           const Tensor& v_cache, bool fp8,
                           const c10::optional<Tensor>& k_scale,
@@ -959,8 +962,16 @@ Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
                           const Tensor* page_table, const Tensor& lengths,
                           const Tensor& slots, int64_t max_len, double scale,
                           int64_t window, int64_t n_chunks, const char* who,
-                          const Tensor* q_lens = nullptr) {
-  if (q_lens) {
+                          const Tensor* q_lens = nullptr,
+                          bool prefill = false) {
+  if (prefill) {
+    TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) &&
+                    q.dim() == 4 && q.size(1) >= 1 &&
+                    q.size(1) < (1LL << 24), who,
+                ": q must be bf16 [n,T,hq,d] with T >= 1, contiguous on GPU, "
+                "got ", q.scalar_type(), " ", q.sizes(), " strides ",
+                q.strides());
+  } else if (q_lens) {
     TORCH_CHECK(q.is_cuda() && q.is_contiguous() && is_bf16(q) &&
                     q.dim() == 4 && q.size(1) >= 1 && q.size(1) <= 16, who,
                 ": q must be bf16 [n,T,hq,d] with 1 <= T <= 16, contiguous "
@@ -1026,7 +1037,8 @@ Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
   const int64_t span = window > 0
       ? std::min(max_len, window + T - 1 + (page_table ? 31 : 0)) : max_len;
   const int64_t groups =
-      q_lens ? decode_multi_groups((int)T, (int)hq, (int)hkv) : 1;
+      prefill ? decode_prefill_groups((int)T, (int)hq, (int)hkv)
+      : q_lens ? decode_multi_groups((int)T, (int)hq, (int)hkv) : 1;
   TORCH_CHECK(hkv * groups <= 65535, who, ": hkv times the column groups of "
               "T * hq / hkv must be <= 65535, got q ", q.sizes());
   const int64_t chunk = decode_batched_split(
@@ -1050,7 +1062,10 @@ Tensor decode_batched_run(const Tensor& q, const Tensor& k_cache,
   if (q_lens) {
     a.q_lens = q_lens->data_ptr<int>();
     a.T = (int)T;
-    decode_multi_launch(a, cur_stream());
+    if (prefill)
+      decode_prefill_launch(a, cur_stream());
+    else
+      decode_multi_launch(a, cur_stream());
   } else {
     decode_batched_launch(a, cur_stream());
   }
@@ -1148,6 +1163,59 @@ Tensor decode_attn_multi_paged_fp8(const Tensor& q, const Tensor& k_cache,
                             &page_table, lengths, slots, max_len, scale,
                             window, n_chunks, "decode_attn_multi_paged_fp8",
                             &q_lens);
+}
+
+// Cache-reading prefill: the multi-token arguments, any T >= 1.
+Tensor decode_attn_prefill(const Tensor& q, const Tensor& k_cache,
+                           const Tensor& v_cache, const Tensor& lengths,
+                           const Tensor& q_lens, const Tensor& slots,
+                           int64_t max_len, double scale, int64_t window,
+                           int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, false, {}, {}, nullptr,
+                            lengths, slots, max_len, scale, window, n_chunks,
+                            "decode_attn_prefill", &q_lens, true);
+}
+
+Tensor decode_attn_prefill_fp8(const Tensor& q, const Tensor& k_cache,
+                               const Tensor& v_cache,
+                               const c10::optional<Tensor>& k_scale,
+                               const c10::optional<Tensor>& v_scale,
+                               const Tensor& lengths, const Tensor& q_lens,
+                               const Tensor& slots, int64_t max_len,
+                               double scale, int64_t window,
+                               int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
+                            nullptr, lengths, slots, max_len, scale, window,
+                            n_chunks, "decode_attn_prefill_fp8", &q_lens,
+                            true);
+}
+
+Tensor decode_attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
+                                 const Tensor& v_cache,
+                                 const Tensor& page_table,
+                                 const Tensor& lengths, const Tensor& q_lens,
+                                 const Tensor& slots, int64_t max_len,
+                                 double scale, int64_t window,
+                                 int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, false, {}, {}, &page_table,
+                            lengths, slots, max_len, scale, window, n_chunks,
+                            "decode_attn_prefill_paged", &q_lens, true);
+}
+
+Tensor decode_attn_prefill_paged_fp8(const Tensor& q, const Tensor& k_cache,
+                                     const Tensor& v_cache,
+                                     const c10::optional<Tensor>& k_scale,
+                                     const c10::optional<Tensor>& v_scale,
+                                     const Tensor& page_table,
+                                     const Tensor& lengths,
+                                     const Tensor& q_lens,
+                                     const Tensor& slots, int64_t max_len,
+                                     double scale, int64_t window,
+                                     int64_t n_chunks) {
+  return decode_batched_run(q, k_cache, v_cache, true, k_scale, v_scale,
+                            &page_table, lengths, slots, max_len, scale,
+                            window, n_chunks, "decode_attn_prefill_paged_fp8",
+                            &q_lens, true);
 }
 
 // Quantise k, v [n,hkv,d] bf16 (any row and head stride that keeps 16-byte
@@ -1509,9 +1577,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_batched_fp8", &decode_attn_batched_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_paged", &decode_attn_paged, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_multi", &decode_attn_multi, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_prefill", &decode_attn_prefill, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_multi_fp8", &decode_attn_multi_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_prefill_fp8", &decode_attn_prefill_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_multi_paged", &decode_attn_multi_paged, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_prefill_paged", &decode_attn_prefill_paged, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_multi_paged_fp8", &decode_attn_multi_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
+  m.def("decode_attn_prefill_paged_fp8", &decode_attn_prefill_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_paged_fp8", &decode_attn_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("kv_append_fp8", &kv_append_fp8, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("positions"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("mfma_probe", &mfma_probe);

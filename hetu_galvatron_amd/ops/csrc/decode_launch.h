@@ -55,6 +55,13 @@ void decode_batched_launch(const DecodeBatchedArgs& a, hipStream_t st);
 int decode_multi_groups(int T, int hq, int hkv);
 void decode_multi_launch(const DecodeBatchedArgs& a, hipStream_t st);
 
+// The prefill-shaped call (decode_attn_prefill.hip): the multi-token call's
+// arguments and semantics for any T >= 1, chunks and part included.
+// decode_prefill_groups: the workgroups per (row, kv head, chunk), one per
+// 128 columns of the T * hq / hkv.
+int decode_prefill_groups(int T, int hq, int hkv);
+void decode_prefill_launch(const DecodeBatchedArgs& a, hipStream_t st);
+
 // k, v: [n, hkv, d] bf16 with row and head strides in elements (multiples of
 // 8, 16-byte aligned bases) and a contiguous last dim; d is 64 or 128.
 void kv_append_fp8_launch(const __bf16* k, const __bf16* v, long k_rs,

@@ -782,9 +782,9 @@ def decode_attention_multi(q: torch.Tensor, k_cache: torch.Tensor,
                            page_table: torch.Tensor = None) -> torch.Tensor:
     """Decode attention of up to T consecutive new tokens per row against
     that row's cache, causal inside the block (speculative verification,
-    chunked decode).
+    chunked decode, chunked prefill).
 
-    q: [n, T, hq, d], 1 <= T <= 16 on the native path; caches, pools, scales,
+    q: [n, T, hq, d], any T >= 1; caches, pools, scales,
     slots, page_table, window and max_len as in `decode_attention_batched`.
     lengths: int32 [n], the row's cached length with the new tokens included
     (the caller has written them); q_lens: int32 [n] in [0, T], how many of
@@ -794,11 +794,17 @@ def decode_attention_multi(q: torch.Tensor, k_cache: torch.Tensor,
     with lengths[i] outside (0, max_len], q_lens[i] outside [0, T] or above
     the length, or a slot outside [0, S).
 
-    Native CDNA4 kernel on GPU bf16 with d in (64, 128), hq/hkv <= 16 and
-    T <= 16 (decode_attn_multi.hip): the T * hq/hkv (token, head) columns of
-    a kv head share one pass over its K and V rows, 32 columns per workgroup.
-    Nothing is read back, so a captured graph replays after lengths, q_lens,
-    slots, the table and the caches change in place.  n_chunks (None: chosen)
+    Native CDNA4 kernels on GPU bf16 with d in (64, 128) and hq/hkv <= 16,
+    for every T.  T <= 16 (decode_attn_multi.hip): the T * hq/hkv (token,
+    head) columns of a kv head share one pass over its K and V rows, 32
+    columns per workgroup, weights as three bf16 terms (the decode element
+    rule).  T > 16 (decode_attn_prefill.hip): the flash-forward shape, 128
+    columns per workgroup over 64-key K/V tiles staged once in LDS (e4m3
+    dequantised while staging); the weights enter the second product as one
+    bf16 term, a relative 2^-9 each, which is the accuracy of
+    `flash_attention_fwd_only` and not that of the decode kernels.  Nothing
+    is read back, so a captured graph replays after lengths, q_lens, slots,
+    the table and the caches change in place.  n_chunks (None: chosen)
     forces the split-KV chunk count.  Elsewhere a loop over (row, token)
     through the torch arithmetic of `decode_attention` at cur = pos + 1.
     """
@@ -810,16 +816,16 @@ def decode_attention_multi(q: torch.Tensor, k_cache: torch.Tensor,
     max_len = max_s if max_len is None else int(max_len)
     fp8 = k_cache.dtype == torch.float8_e4m3fn
     if q.is_cuda and native_available() and q.dtype == torch.bfloat16 \
-            and d in (64, 128) and hq // hkv <= 16 and T <= 16:
+            and d in (64, 128) and hq // hkv <= 16:
         ext = get_ext()
         tail = (lengths, q_lens, slots, max_len, float(scale),
                 int(window or 0), int(n_chunks or 0))
         sc = (k_scale, v_scale) if fp8 else ()
+        name = "decode_attn_multi" if T <= 16 else "decode_attn_prefill"
         if page_table is not None:
-            f = ext.decode_attn_multi_paged_fp8 if fp8 \
-                else ext.decode_attn_multi_paged
+            f = getattr(ext, name + ("_paged_fp8" if fp8 else "_paged"))
             return f(q.contiguous(), k_cache, v_cache, *sc, page_table, *tail)
-        f = ext.decode_attn_multi_fp8 if fp8 else ext.decode_attn_multi
+        f = getattr(ext, name + ("_fp8" if fp8 else ""))
         return f(q.contiguous(), k_cache, v_cache, *sc, *tail)
     return _decode_attention_multi_torch(
         q, k_cache, v_cache, lengths, q_lens, slots, S, max_len, scale,

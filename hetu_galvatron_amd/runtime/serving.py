@@ -38,6 +38,13 @@ one `decode_attention_multi` call per layer attends each of them causally.
 Greedy acceptance emits the model's own tokens while the drafts agree with
 them, so the output is that of plain greedy decoding in fewer steps.  Drafts
 come from prompt lookup (`ngram_draft`) or a `draft_fn`.
+
+`prefill_chunk=N` (batched attention only; every cache kind) runs a prompt in
+consecutive chunks of at most N tokens.  Each chunk writes its K/V to the
+slot's cache first and then attends the cache through one
+`decode_attention_multi` call per layer, so prefill reads what decode will
+read (the quantised rows of an fp8 cache) and a long prompt's activations are
+bounded by the chunk.  `add_request` still returns the first token at once.
 """
 from __future__ import annotations
 
@@ -88,7 +95,8 @@ class ContinuousBatchingEngine:
                  batched_attention: bool = False, kv_cache_dtype: str = None,
                  kv_scales: torch.Tensor = None, page_size: int = None,
                  num_pages: int = None, speculative_tokens: int = 0,
-                 draft_fn: Callable[[List[int], int], List[int]] = None):
+                 draft_fn: Callable[[List[int], int], List[int]] = None,
+                 prefill_chunk: int = None):
         """kv_cache_dtype: None (the model's dtype) or "fp8"; kv_scales:
         fp32 [n_layers, 2, hkv] dequantisation scales of the fp8 cache
         (k, v per layer; None: ones).  page_size: None (one contiguous row
@@ -98,7 +106,17 @@ class ContinuousBatchingEngine:
         speculative_tokens: drafts verified per slot and step (0: plain
         decode; `step()` then returns one token per request, otherwise a
         list); draft_fn(history, k) -> up to k proposed tokens replaces the
-        prompt-lookup drafter.  Slots that sample take no drafts."""
+        prompt-lookup drafter.  Slots that sample take no drafts.
+        prefill_chunk: None (the whole prompt through flash on its fresh
+        K/V) or the most tokens of a prompt run at once, a power of two
+        >= 32 (batched attention only): every chunk attends the cache."""
+        if prefill_chunk is not None:
+            if not batched_attention:
+                raise ValueError("prefill_chunk needs batched_attention=True")
+            if prefill_chunk < 32 or prefill_chunk & (prefill_chunk - 1):
+                raise ValueError(f"prefill_chunk must be a power of two "
+                                 f">= 32, got {prefill_chunk}")
+        self.prefill_chunk = prefill_chunk
         if speculative_tokens < 0:
             raise ValueError("speculative_tokens must be >= 0")
         if speculative_tokens and not batched_attention:
@@ -205,7 +223,10 @@ class ContinuousBatchingEngine:
         else:
             # single-slot prefill on the slot's contiguous cache row
             view = _SlotCache(self.cache, slot)
-        logits = self._prefill(prompt_ids.unsqueeze(0), view)
+        if self.prefill_chunk is None:
+            logits = self._prefill(prompt_ids.unsqueeze(0), view)
+        else:
+            logits = self._prefill_chunked(prompt_ids.unsqueeze(0), view, slot)
         if temperature > 0:
             g = torch.Generator(device="cpu").manual_seed(seed)
             self.samplers[slot] = (temperature, g)
@@ -268,6 +289,55 @@ class ContinuousBatchingEngine:
             h = residual + attn.linear_proj(o)
             residual = h
             h = residual + layer.mlp(layer.post_attn_norm(h))
+        h = gen.final_norm.norm(h[-1:])
+        return gen.lm_head.lm_head(h)[0].float()
+
+    @torch.no_grad()
+    def _prefill_chunked(self, ids: torch.Tensor, view: "_SlotCache",
+                         slot: int):
+        """The prompt in consecutive chunks of at most `prefill_chunk`
+        tokens.  Per chunk and layer: RoPE at the chunk's positions, K/V into
+        the slot's cache rows or pages (quantised for fp8), then one
+        `decode_attention_multi` call of the chunk's tokens against the
+        cache, the first chunk included: prefill attends what decode will
+        attend.  Only the last chunk computes logits."""
+        gen, dev, cache = self.gen, self.gen._dev, self.cache
+        sp = ids.shape[1]
+        i32 = dict(dtype=torch.int32, device=dev)
+        slot32 = torch.tensor([slot], **i32)
+        paged = {} if self.page_size is None \
+            else {"page_table": self.page_table}
+        for pos in range(0, sp, self.prefill_chunk):
+            c = min(self.prefill_chunk, sp - pos)
+            lengths_t = torch.tensor([pos + c], **i32)
+            q_lens_t = torch.tensor([c], **i32)
+            h = gen.embedding.word_embeddings(ids[:, pos:pos + c])
+            for li, layer in enumerate(gen.layers):
+                attn = layer.attention
+                residual = h
+                x = layer.input_norm(h)
+                q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
+                if getattr(attn, "q_layernorm", None) is not None:
+                    q = attn.q_layernorm(q)
+                    k = attn.k_layernorm(k)
+                if layer.rotary is not None:
+                    cos, sin = layer.rotary.full_tables(self.max_seq, dev)
+                    from .transformer.rope import apply_rope_qk
+                    q, k = apply_rope_qk(q.contiguous(), k.contiguous(),
+                                         cos[pos:pos + c], sin[pos:pos + c],
+                                         interleaved=getattr(
+                                             attn, "rope_interleaved", False))
+                view.write(li, k.permute(1, 0, 2, 3), v.permute(1, 0, 2, 3),
+                           pos)
+                o = decode_attention_multi(
+                    q.permute(1, 0, 2, 3).contiguous(), cache.k[li],
+                    cache.v[li], lengths_t, q_lens_t, slot32,
+                    window=getattr(gen, "window", None), max_len=pos + c,
+                    softmax_scale=gen.scale, k_scale=cache.k_scale[li],
+                    v_scale=cache.v_scale[li], **paged)
+                h = residual + attn.linear_proj(o.reshape(c, 1, -1))
+                residual = h
+                h = residual + layer.mlp(layer.post_attn_norm(h))
         h = gen.final_norm.norm(h[-1:])
         return gen.lm_head.lm_head(h)[0].float()
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|decode-multi|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|decode-multi|decode-prefill|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -454,6 +454,72 @@ def bench_decode_multi(iters, repeats=9, expanded_only=False):
                                   f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
 
 
+def bench_decode_prefill(iters, repeats=9, baseline_only=False):
+    """ops.decode_attention_multi at T in (64, 256, 1024) new tokens per row
+    against a cache of 4096 (the prefill kernels) beside what the engine did
+    for the same work without them: flash_attention_fwd_only on a gathered
+    bf16 contiguous copy of the row's K/V, the copy (gather, dequantisation)
+    included.  h32/8 d128, n in (1, 8), bf16 and e4m3, contiguous and page
+    32.  baseline_only times only the copy + flash rows (to time a build of
+    the extension that predates the prefill kernels with the same code)."""
+    from hetu_galvatron_amd import ops
+    hq, hkv, d, L, page = 32, 8, 128, 4096, 32
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in (1, 8):
+        kc, vc = (torch.randn(n, L, hkv, d, device="cuda",
+                              generator=g).bfloat16() for _ in "kv")
+        ks = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        vs = 0.5 + torch.rand(hkv, device="cuda", generator=g)
+        k8 = (kc.float() / ks[:, None]).to(torch.float8_e4m3fn)
+        v8 = (vc.float() / vs[:, None]).to(torch.float8_e4m3fn)
+        slots = torch.arange(n, dtype=torch.int32, device="cuda")
+        lengths = torch.full((n,), L, dtype=torch.int32, device="cuda")
+        P = n * L // page
+        perm = torch.randperm(P, device="cuda", generator=g)
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(P, device="cuda")
+        table = perm.int().reshape(n, -1)
+        pool = [c.view(P, page, hkv, d)[inv].contiguous()
+                for c in (kc, vc, k8, v8)]
+        for T in (64, 256, 1024):
+            q = torch.randn(n, T, hq, d, device="cuda", generator=g).bfloat16()
+            q_lens = torch.full((n,), T, dtype=torch.int32, device="cuda")
+            for name, k, sc in (("bf16", 0, None), ("fp8", 2, (ks, vs))):
+                for what, kk, vv, tb in (
+                        ("contiguous", (kc, vc, k8, v8)[k],
+                         (kc, vc, k8, v8)[k + 1], None),
+                        ("page 32", pool[k], pool[k + 1], table)):
+                    def copy(c, s):
+                        if tb is not None:       # gather the rows' pages
+                            c = c[tb.long()].reshape(n, L, hkv, d)
+                        if sc is not None:       # dequantise
+                            return (c.float() * s[:, None]).bfloat16()
+                        return c.clone() if tb is None else c
+
+                    def flash():
+                        return ops.flash_attention_fwd_only(
+                            q, copy(kk, sc and sc[0]), copy(vv, sc and sc[1]),
+                            causal=True, softmax_scale=d ** -0.5)[0]
+
+                    def prefill():
+                        kw = {} if sc is None else dict(k_scale=sc[0],
+                                                        v_scale=sc[1])
+                        return ops.decode_attention_multi(
+                            q, kk, vv, lengths, q_lens, slots, max_len=L,
+                            page_table=tb, **kw)
+
+                    rows = [("copy+flash", flash)]
+                    if not baseline_only:
+                        rows.append(("prefill", prefill))
+                        err = (prefill().float() - flash().float()).abs().max()
+                        assert float(err) < 0.05, "prefill != flash"
+                    for how, fn in rows:
+                        t, lo, hi = median_of_windows(fn, iters, repeats)
+                        print(f"decode-prefill n{n} T{T:<4d} {name:4s} "
+                              f"{what:10s} {how:10s} {t*1e6:8.1f} us "
+                              f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -545,6 +611,8 @@ def main():
                     help="decode-paged entry: skip the paged pools")
     ap.add_argument("--expanded-only", action="store_true",
                     help="decode-multi entry: time only the expanded rows")
+    ap.add_argument("--baseline-only", action="store_true",
+                    help="decode-prefill entry: time only copy + flash")
     ap.add_argument("--composition-only", action="store_true",
                     help="qkv-varlen entry: time only the composition")
     args = ap.parse_args()
@@ -563,6 +631,8 @@ def main():
                it, args.repeats, args.contiguous_only),
            "decode-multi": lambda it: bench_decode_multi(
                it, args.repeats, args.expanded_only),
+           "decode-prefill": lambda it: bench_decode_prefill(
+               it, args.repeats, args.baseline_only),
            "qkv-varlen": lambda it: bench_qkv_varlen(
                it, args.repeats, args.composition_only)}
     if args.what == "all":
