@@ -5,6 +5,6 @@ from .functional import (  # noqa: F401
     fused_qkv_attention_varlen,
     flash_attention_fwd_only, flash_attention_bwd_only, flash_bias_attention,
     decode_attention, decode_attention_batched, decode_attention_multi,
-    kv_cache_append,
+    kv_cache_append, rope_kv_append,
 )
 from . import reference_ops  # noqa: F401

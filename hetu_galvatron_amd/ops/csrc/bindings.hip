@@ -1261,6 +1261,109 @@ void kv_append_fp8(const Tensor& k, const Tensor& v, Tensor& k_cache,
       (int)d, (int)k_cache.size(0), (int)k_cache.size(1), cur_stream());
 }
 
+// The decode prologue (DecodePrologueArgs in decode_launch.h): qkv is the
+// packed linear output of n*T token rows, n = lengths.size(0), viewed as
+// [n,T,G,qpg+2,d] with d the caches' head dim -> q [n,T,G*qpg,d].
+Tensor rope_kv_append(const Tensor& qkv, int64_t num_groups,
+                      int64_t q_per_group, const c10::optional<Tensor>& cos,
+                      const c10::optional<Tensor>& sin, const Tensor& lengths,
+                      const Tensor& q_lens, const Tensor& slots,
+                      Tensor& k_cache, Tensor& v_cache,
+                      const c10::optional<Tensor>& k_scale,
+                      const c10::optional<Tensor>& v_scale,
+                      const c10::optional<Tensor>& page_table,
+                      bool interleaved) {
+  const char* who = "rope_kv_append";
+  const int64_t G = num_groups, qpg = q_per_group, n = lengths.size(0);
+  TORCH_CHECK(k_cache.dim() == 4, who, ": k_cache must be [S,max_s,hkv,d], "
+              "got ", k_cache.sizes());
+  const int64_t d = k_cache.size(3), row = G * (qpg + 2) * d;
+  TORCH_CHECK(G >= 1 && qpg >= 1 && lengths.dim() == 1 && n >= 1 &&
+                  k_cache.size(2) == G, who, ": needs num_groups >= 1 equal to "
+              "the caches' hkv, q_per_group >= 1 and n >= 1, got num_groups ",
+              G, " q_per_group ", qpg, " k_cache ", k_cache.sizes(),
+              " lengths ", lengths.sizes());
+  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && is_bf16(qkv) &&
+                  qkv.numel() > 0 && qkv.numel() % (n * row) == 0 &&
+                  qkv.numel() < (1LL << 34) &&
+                  reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              who, ": qkv must be bf16, contiguous and 16-byte aligned on "
+              "GPU with n*T rows of G*(qpg+2)*d = ", row, " elements (n = ",
+              n, "), got ", qkv.scalar_type(), " ", qkv.sizes());
+  const int64_t T = qkv.numel() / (n * row);
+  const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  check_kv_caches(k_cache, v_cache, fp8 ? at::kFloat8_e4m3fn : at::kBFloat16,
+                  qkv.device(), d, who);
+  DecodePrologueArgs a{};
+  a.fp8 = fp8;
+  if (fp8) {
+    a.k_scale = fp8_scale_ptr(k_scale, qkv.device(), G, who, "k_scale");
+    a.v_scale = fp8_scale_ptr(v_scale, qkv.device(), G, who, "v_scale");
+  }
+  int64_t lim = k_cache.size(1);             // positions a row can hold
+  if (page_table) {
+    const Tensor& t = *page_table;
+    const int64_t page = k_cache.size(1);
+    TORCH_CHECK(page >= 32 && (page & (page - 1)) == 0, who,
+                ": page (k_cache.size(1)) must be a power of two >= 32, got ",
+                page, " for k_cache ", k_cache.sizes());
+    TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() &&
+                    t.scalar_type() == at::kInt && t.is_contiguous() &&
+                    t.dim() == 2 && t.size(0) > 0 && t.size(1) > 0 &&
+                    t.size(1) * page < (1LL << 31), who,
+                ": page_table must be int32 [S,max_pages] contiguous on qkv's "
+                "GPU, got ", t.scalar_type(), " ", t.sizes(), " on ",
+                t.device());
+    a.table = t.data_ptr<int>();
+    a.S = (int)t.size(0);
+    a.max_pages = (int)t.size(1);
+    a.P = (int)k_cache.size(0);
+    while ((1LL << a.lg) < page) ++a.lg;
+    lim = t.size(1) * page;
+  } else {
+    TORCH_CHECK(lim < (1LL << 31), who, ": max_s must be < 2^31, got k_cache ",
+                k_cache.sizes());
+    a.S = (int)k_cache.size(0);
+    a.max_s = (int)k_cache.size(1);
+  }
+  TORCH_CHECK(cos.has_value() == sin.has_value(), who,
+              ": cos and sin come together or not at all");
+  if (cos) {
+    auto check_table = [&](const Tensor& t, const char* name) {
+      TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() &&
+                      t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                      t.dim() == 2 && t.size(0) >= 1 && t.size(1) == d / 2 &&
+                      reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                  who, ": ", name, " must be fp32 [rows,d/2] contiguous and "
+                  "16-byte aligned on qkv's GPU (d = ", d, "), got ",
+                  t.scalar_type(), " ", t.sizes(), " on ", t.device());
+    };
+    check_table(*cos, "cos");
+    check_table(*sin, "sin");
+    TORCH_CHECK(sin->size(0) == cos->size(0), who, ": cos and sin differ in "
+                "rows: ", cos->sizes(), " and ", sin->sizes());
+    a.cos = cos->data_ptr<float>();
+    a.sin = sin->data_ptr<float>();
+    lim = std::min<int64_t>(lim, cos->size(0));
+  }
+  check_i32_rows(lengths, qkv.device(), n, who, "lengths");
+  check_i32_rows(q_lens, qkv.device(), n, who, "q_lens");
+  check_i32_rows(slots, qkv.device(), n, who, "slots");
+  auto q = at::empty({n, T, G * qpg, d}, qkv.options());
+  a.qkv = bfp(qkv);
+  a.interleaved = interleaved;
+  a.lengths = lengths.data_ptr<int>();
+  a.q_lens = q_lens.data_ptr<int>();
+  a.slots = slots.data_ptr<int>();
+  a.q = bfp_mut(q);
+  a.k_cache = k_cache.data_ptr();
+  a.v_cache = v_cache.data_ptr();
+  a.n = (int)n; a.T = (int)T; a.G = (int)G; a.qpg = (int)qpg; a.d = (int)d;
+  a.lim = (int)lim;
+  decode_prologue_launch(a, cur_stream());
+  return q;
+}
+
 Tensor mfma_probe(const Tensor& A, const Tensor& B, bool alt) {
   CHECK_GPU(A); CHECK_GPU(B);
   auto D = at::zeros({32, 32}, A.options().dtype(at::kFloat));
@@ -1586,6 +1689,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_prefill_paged_fp8", &decode_attn_prefill_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("decode_attn_paged_fp8", &decode_attn_paged_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("page_table"), py::arg("lengths"), py::arg("slots"), py::arg("max_len"), py::arg("scale"), py::arg("window") = 0, py::arg("n_chunks") = 0);
   m.def("kv_append_fp8", &kv_append_fp8, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("positions"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+  m.def("rope_kv_append", &rope_kv_append, py::arg("qkv"), py::arg("num_groups"), py::arg("q_per_group"), py::arg("cos"), py::arg("sin"), py::arg("lengths"), py::arg("q_lens"), py::arg("slots"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("page_table") = py::none(), py::arg("interleaved") = false);
   m.def("mfma_probe", &mfma_probe);
   m.def("ce_max", &ce_max);
   m.def("ce_sum_target", &ce_sum_target);

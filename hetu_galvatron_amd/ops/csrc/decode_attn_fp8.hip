@@ -11,9 +11,9 @@
                              apply_to = function)
 #endif
 
-namespace {
+#include "decode_quant.h"
 
-constexpr float F8_MAX = 448.f;                 // largest finite e4m3
+namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned f8_uint4;
 
@@ -49,14 +49,7 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(
   for (int j = 0; j < 8; ++j) { x[j] = (float)lo[j]; x[8 + j] = (float)hi[j]; }
   f8_uint4 out;
 #pragma unroll
-  for (int j = 0; j < 16; ++j)
-    x[j] = fminf(fmaxf(x[j] / sc, -F8_MAX), F8_MAX);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    int wd = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * j], x[4 * j + 1], 0, false);
-    wd = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * j + 2], x[4 * j + 3], wd, true);
-    out[j] = (unsigned)wd;
-  }
+  for (int j = 0; j < 4; ++j) out[j] = db_quant_e4m3x4(x + 4 * j, sc);
   uint8_t* dst = (is_v ? vc : kc) +
                  (((long)slot * max_s + pos) * hkv + h) * d + 16 * ch;
   *reinterpret_cast<f8_uint4*>(dst) = out;

@@ -70,3 +70,40 @@ void kv_append_fp8_launch(const __bf16* k, const __bf16* v, long k_rs,
                           const float* v_scale, const int* slots,
                           const int* positions, int n, int hkv, int d, int S,
                           int max_s, hipStream_t st);
+
+// The decode prologue (decode_prologue.hip): per-row RoPE of q and k and the
+// cache write of k and v, one launch for the n*T rows of the packed qkv
+// [n, T, G, qpg+2, d] (slots 0..qpg-1 of a group its q heads, qpg k, qpg+1
+// v).  Token t of row i sits at p = lengths[i] - q_lens[i] + t and is live
+// when t < q_lens[i], slots[i] is in [0, S) and 0 <= p < lim, where lim is
+// min(rows of cos/sin, positions of a cache row or of a table row's pages),
+// set by the caller.  q [n, T, G*qpg, d] gets the rotated heads of a live
+// token and zeros otherwise; a live token's rotated k and its v go to
+// cache[slots[i], p] (contiguous) or to pool[table[slots[i], p >> lg],
+// p & (page - 1)], nowhere when that page id is outside [0, P).  cos, sin:
+// fp32 [rows, d/2], both null for no rotation.  Caches, scales, table, S,
+// max_s, max_pages, lg and P as in DecodeBatchedArgs with hkv = G; d is 64 or
+// 128.
+struct DecodePrologueArgs {
+  const __bf16* qkv;
+  const float* cos;
+  const float* sin;
+  bool interleaved;          // pairs (2m, 2m+1), not (m, m + d/2)
+  const int* lengths;
+  const int* q_lens;
+  const int* slots;
+  const int* table;
+  __bf16* q;
+  void* k_cache;
+  void* v_cache;
+  bool fp8;
+  const float* k_scale;
+  const float* v_scale;
+  int n, T, G, qpg, d;
+  int lim;
+  int S;
+  int max_s;                 // contiguous only
+  int max_pages, lg, P;      // paged only
+};
+
+void decode_prologue_launch(const DecodePrologueArgs& a, hipStream_t st);

@@ -979,3 +979,101 @@ def _kv_cache_append_torch(k, v, k_cache, v_cache, slots, positions,
                 x = x / scale.float()[:, None]
             x = x.clamp(-448.0, 448.0)
         cache[sl, ps] = x.to(cache.dtype)
+
+
+@torch.no_grad()
+def rope_kv_append(qkv: torch.Tensor, num_groups: int, q_per_group: int,
+                   cos: Optional[torch.Tensor], sin: Optional[torch.Tensor],
+                   lengths: torch.Tensor, q_lens: torch.Tensor,
+                   slots: torch.Tensor, k_cache: torch.Tensor,
+                   v_cache: torch.Tensor, k_scale: torch.Tensor = None,
+                   v_scale: torch.Tensor = None,
+                   page_table: torch.Tensor = None,
+                   interleaved: bool = False) -> torch.Tensor:
+    """The decode prologue: per-row RoPE of q and k and the cache write of k
+    and v for the new tokens of a serving step, from the packed qkv linear
+    output.  Returns q [n, T, G*qpg, D], ready for `decode_attention_multi`
+    (or, T = 1, `decode_attention_batched` on q[:, 0]).
+
+    qkv: the `linear_qkv` output of n*T token rows, contiguous, viewed as
+    [n, T, G, qpg+2, D] (G = num_groups, qpg = q_per_group): slots 0..qpg-1
+    of a group are its q heads, slot qpg is k and slot qpg+1 is v, the layout
+    of `fused_qkv_attention`.  It is not modified.  lengths, q_lens, slots:
+    the int32 [n] device tensors of `decode_attention_multi`, lengths with the
+    new tokens counted.  cos, sin: fp32 [rows, D/2] position tables (None:
+    no rotation).  Caches, scales and page_table as in
+    `decode_attention_batched`, hkv = G; scales as in `kv_cache_append`.
+
+    Token t of row i sits at p = lengths[i] - q_lens[i] + t.  It is live when
+    t < q_lens[i], slots[i] is inside the caches (the table) and
+    0 <= p < min(rows, capacity), capacity = max_s or max_pages * page.  A
+    live token gets its q heads rotated at p and its rotated k and its v
+    stored at position p of its cache row, or of its page; when that page id
+    is outside [0, P) nothing is stored.  Any other token gets a zero q row
+    and stores nothing.  The rotation is fp32 with every product and sum
+    rounded on its own, then rounded to the input dtype: pairs (j, j + D/2),
+    or (2j, 2j + 1) when interleaved.  e4m3 caches store what
+    `kv_cache_append` stores for the rotated k and for v.
+
+    Native CDNA4 kernel on GPU bf16 with D in (64, 128)
+    (decode_prologue.hip): one launch, positions, cache rows and page ids
+    read on the device, nothing read back.  Elsewhere the same arithmetic in
+    torch, bit for bit.
+    """
+    D = k_cache.shape[-1]
+    if qkv.is_cuda and native_available() and qkv.dtype == torch.bfloat16 \
+            and D in (64, 128) \
+            and k_cache.dtype in (torch.bfloat16, torch.float8_e4m3fn):
+        return get_ext().rope_kv_append(
+            qkv, num_groups, q_per_group, cos, sin, lengths, q_lens, slots,
+            k_cache, v_cache, k_scale, v_scale, page_table, interleaved)
+    return _rope_kv_append_torch(
+        qkv, num_groups, q_per_group, cos, sin, lengths, q_lens, slots,
+        k_cache, v_cache, k_scale, v_scale, page_table, interleaved)
+
+
+def _rope_pairs_torch(x, c, s, interleaved):
+    """x [..., D] rotated by c, s (broadcastable to [..., D/2]) in fp32, each
+    product and sum rounded on its own, rounded back to x's dtype."""
+    d2 = x.shape[-1] // 2
+    if interleaved:
+        x1, x2 = x[..., 0::2].float(), x[..., 1::2].float()
+        y = torch.empty_like(x, dtype=torch.float32)
+        y[..., 0::2] = x1 * c - x2 * s
+        y[..., 1::2] = x2 * c + x1 * s
+        return y.to(x.dtype)
+    x1, x2 = x[..., :d2].float(), x[..., d2:].float()
+    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(x.dtype)
+
+
+def _rope_kv_append_torch(qkv, G, qpg, cos, sin, lengths, q_lens, slots,
+                          k_cache, v_cache, k_scale, v_scale, page_table,
+                          interleaved):
+    n, D = lengths.shape[0], k_cache.shape[-1]
+    x = qkv.reshape(n, -1, G, qpg + 2, D)
+    T = x.shape[1]
+    if page_table is None:
+        S, cap = k_cache.shape[:2]
+    else:
+        S, cap = page_table.shape[0], page_table.shape[1] * k_cache.shape[1]
+    lim = cap if cos is None else min(cap, cos.shape[0])
+    t = torch.arange(T, device=qkv.device)
+    sl = slots.long()[:, None].expand(n, T)
+    pos = (lengths.long() - q_lens.long())[:, None] + t
+    live = (t < q_lens[:, None]) & (sl >= 0) & (sl < S) & (pos >= 0) \
+        & (pos < lim)
+    q, k, v = x[..., :qpg, :], x[..., qpg, :], x[..., qpg + 1, :]
+    if cos is not None:
+        p = pos.clamp(0, lim - 1)
+        c, s = cos[p].float(), sin[p].float()            # [n, T, D/2]
+        q = _rope_pairs_torch(q, c[:, :, None, None], s[:, :, None, None],
+                              interleaved)
+        k = _rope_pairs_torch(k, c[:, :, None], s[:, :, None], interleaved)
+    q = torch.where(live[:, :, None, None, None], q, torch.zeros_like(q))
+    sl, pos, k, v = sl[live], pos[live], k[live], v[live]
+    if page_table is not None:
+        lg = k_cache.shape[1].bit_length() - 1
+        sl = page_table.to(sl.device)[sl, pos >> lg].long()
+        pos = pos & (k_cache.shape[1] - 1)
+    _kv_cache_append_torch(k, v, k_cache, v_cache, sl, pos, k_scale, v_scale)
+    return q.reshape(n, T, G * qpg, D)

@@ -45,6 +45,14 @@ slot's cache first and then attends the cache through one
 `decode_attention_multi` call per layer, so prefill reads what decode will
 read (the quantised rows of an fp8 cache) and a long prompt's activations are
 bounded by the chunk.  `add_request` still returns the first token at once.
+
+`fused_prologue=True` (batched attention only; every cache kind, decode,
+speculative steps and chunked prefill) replaces what stands between the qkv
+linear and the attention call of a layer (the split, the table gathers, the
+rotation of q and k and the cache write) by one `rope_kv_append` call on the
+packed qkv output.  Positions, cache rows and page ids come from the device
+tensors that attention reads, so the step builds no per-row write indices on
+the host.  The tokens are those of the unfused engine.
 """
 from __future__ import annotations
 
@@ -54,7 +62,7 @@ import torch
 
 from ..ops import (decode_attention, decode_attention_batched,
                    decode_attention_multi, flash_attention_fwd_only,
-                   kv_cache_append)
+                   kv_cache_append, rope_kv_append)
 from .inference import GalvatronGenerator, KVCache
 
 __all__ = ["ContinuousBatchingEngine", "ngram_draft"]
@@ -96,7 +104,7 @@ class ContinuousBatchingEngine:
                  kv_scales: torch.Tensor = None, page_size: int = None,
                  num_pages: int = None, speculative_tokens: int = 0,
                  draft_fn: Callable[[List[int], int], List[int]] = None,
-                 prefill_chunk: int = None):
+                 prefill_chunk: int = None, fused_prologue: bool = False):
         """kv_cache_dtype: None (the model's dtype) or "fp8"; kv_scales:
         fp32 [n_layers, 2, hkv] dequantisation scales of the fp8 cache
         (k, v per layer; None: ones).  page_size: None (one contiguous row
@@ -109,7 +117,14 @@ class ContinuousBatchingEngine:
         prompt-lookup drafter.  Slots that sample take no drafts.
         prefill_chunk: None (the whole prompt through flash on its fresh
         K/V) or the most tokens of a prompt run at once, a power of two
-        >= 32 (batched attention only): every chunk attends the cache."""
+        >= 32 (batched attention only): every chunk attends the cache.
+        fused_prologue: RoPE and the cache write of decode steps,
+        speculative steps and prefill chunks through one `rope_kv_append`
+        call per layer (batched attention only).  A layer with `q_layernorm`
+        keeps the unfused composition, because the norm sits between the
+        split and the rotation."""
+        if fused_prologue and not batched_attention:
+            raise ValueError("fused_prologue needs batched_attention=True")
         if prefill_chunk is not None:
             if not batched_attention:
                 raise ValueError("prefill_chunk needs batched_attention=True")
@@ -151,6 +166,10 @@ class ContinuousBatchingEngine:
         self.margs = m
         self.max_slots = max_slots
         self.max_seq = max_seq
+        # per layer: does the fused prologue run it?
+        self._fused = [fused_prologue and getattr(
+            layer.attention, "q_layernorm", None) is None
+            for layer in self.gen.layers]
         dtype = torch.float8_e4m3fn if kv_cache_dtype == "fp8" \
             else next(self.gen.embedding.parameters()).dtype
         if page_size is None:
@@ -260,6 +279,21 @@ class ContinuousBatchingEngine:
             self.page_table[slot, first:len(own)] = torch.tensor(
                 own[first:], dtype=torch.int32, device=self.page_table.device)
 
+    def _prologue(self, li: int, layer, x: torch.Tensor, lengths_t, q_lens_t,
+                  slot32, paged) -> torch.Tensor:
+        """Layer li's fused prologue on the normed rows x (n*T of them, row
+        major in (slot row, token)): qkv linear, then one `rope_kv_append`,
+        which leaves K/V in the cache.  -> q [n, T, hq, d]"""
+        attn, cache = layer.attention, self.cache
+        cos = sin = None
+        if layer.rotary is not None:
+            cos, sin = layer.rotary.full_tables(self.max_seq, self.gen._dev)
+        return rope_kv_append(
+            attn.linear_qkv(x), attn.num_groups_local, attn.q_per_group, cos,
+            sin, lengths_t, q_lens_t, slot32, cache.k[li], cache.v[li],
+            cache.k_scale[li], cache.v_scale[li],
+            interleaved=getattr(attn, "rope_interleaved", False), **paged)
+
     def _prefill(self, ids: torch.Tensor, view: "_SlotCache"):
         gen = self.gen
         h = gen.embedding.word_embeddings(ids)
@@ -316,22 +350,26 @@ class ContinuousBatchingEngine:
                 attn = layer.attention
                 residual = h
                 x = layer.input_norm(h)
-                q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
-                if getattr(attn, "q_layernorm", None) is not None:
-                    q = attn.q_layernorm(q)
-                    k = attn.k_layernorm(k)
-                if layer.rotary is not None:
-                    cos, sin = layer.rotary.full_tables(self.max_seq, dev)
-                    from .transformer.rope import apply_rope_qk
-                    q, k = apply_rope_qk(q.contiguous(), k.contiguous(),
-                                         cos[pos:pos + c], sin[pos:pos + c],
-                                         interleaved=getattr(
-                                             attn, "rope_interleaved", False))
-                view.write(li, k.permute(1, 0, 2, 3), v.permute(1, 0, 2, 3),
-                           pos)
+                if self._fused[li]:
+                    q = self._prologue(li, layer, x, lengths_t, q_lens_t,
+                                       slot32, paged)
+                else:
+                    q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
+                    if getattr(attn, "q_layernorm", None) is not None:
+                        q = attn.q_layernorm(q)
+                        k = attn.k_layernorm(k)
+                    if layer.rotary is not None:
+                        cos, sin = layer.rotary.full_tables(self.max_seq, dev)
+                        from .transformer.rope import apply_rope_qk
+                        q, k = apply_rope_qk(
+                            q.contiguous(), k.contiguous(), cos[pos:pos + c],
+                            sin[pos:pos + c], interleaved=getattr(
+                                attn, "rope_interleaved", False))
+                    view.write(li, k.permute(1, 0, 2, 3),
+                               v.permute(1, 0, 2, 3), pos)
+                    q = q.permute(1, 0, 2, 3).contiguous()
                 o = decode_attention_multi(
-                    q.permute(1, 0, 2, 3).contiguous(), cache.k[li],
-                    cache.v[li], lengths_t, q_lens_t, slot32,
+                    q, cache.k[li], cache.v[li], lengths_t, q_lens_t, slot32,
                     window=getattr(gen, "window", None), max_len=pos + c,
                     softmax_scale=gen.scale, k_scale=cache.k_scale[li],
                     v_scale=cache.v_scale[li], **paged)
@@ -361,36 +399,46 @@ class ContinuousBatchingEngine:
             slot32 = slot_t.int()
             # where the new rows go: (cache row, position), or paged
             # (page id, offset in the page)
-            wr_t, wr_pos = slot_t, pos
             if self.page_size is not None:
                 for s in active:         # a length that crosses a boundary
                     self._grow(s, self.lengths[s] + 1)
-                wr_t = torch.tensor(
-                    [self.pages[s][self.lengths[s] // self.page_size]
-                     for s in active], device=dev)
-                wr_pos = pos % self.page_size
-            wr32, wr_pos32 = wr_t.int(), wr_pos.int()
+            if not all(self._fused):     # the fused prologue needs none
+                wr_t, wr_pos = slot_t, pos
+                if self.page_size is not None:
+                    wr_t = torch.tensor(
+                        [self.pages[s][self.lengths[s] // self.page_size]
+                         for s in active], device=dev)
+                    wr_pos = pos % self.page_size
+                wr32, wr_pos32 = wr_t.int(), wr_pos.int()
             paged = {} if self.page_size is None \
                 else {"page_table": self.page_table}
             lengths_t = (pos + 1).int()      # the new token is attended too
+            if any(self._fused):
+                q_lens_t = torch.ones_like(lengths_t)
             max_len = max(self.lengths[s] for s in active) + 1
         h = gen.embedding.word_embeddings(ids.transpose(0, 1))  # [1, n, hd]
         for li, layer in enumerate(gen.layers):
             attn = layer.attention
             residual = h
             x = layer.input_norm(h)
-            q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
-            if getattr(attn, "q_layernorm", None) is not None:
-                q = attn.q_layernorm(q)
-                k = attn.k_layernorm(k)
-            if layer.rotary is not None:
-                cos_t, sin_t = layer.rotary.full_tables(self.max_seq, dev)
-                il = getattr(attn, "rope_interleaved", False)
-                q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
-                k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
+            if self._fused[li]:          # K/V are in the cache after this
+                q = self._prologue(li, layer, x, lengths_t, q_lens_t, slot32,
+                                   paged).transpose(0, 1)   # [1, n, hq, d]
+            else:
+                q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
+                if getattr(attn, "q_layernorm", None) is not None:
+                    q = attn.q_layernorm(q)
+                    k = attn.k_layernorm(k)
+                if layer.rotary is not None:
+                    cos_t, sin_t = layer.rotary.full_tables(self.max_seq, dev)
+                    il = getattr(attn, "rope_interleaved", False)
+                    q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
+                    k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
             if self.batched_attention:
                 cache = self.cache
-                if cache.fp8:
+                if self._fused[li]:
+                    pass
+                elif cache.fp8:
                     kv_cache_append(k[0], v[0], cache.k[li], cache.v[li],
                                     wr32, wr_pos32, cache.k_scale[li],
                                     cache.v_scale[li])
@@ -447,23 +495,25 @@ class ContinuousBatchingEngine:
         ids = torch.tensor([[self.last_tok[s]] + d + [0] * (T - 1 - len(d))
                             for s, d in zip(active, drafts)], device=dev)
         base = torch.tensor([self.lengths[s] for s in active], device=dev)
-        pos = (base[:, None] + torch.arange(T, device=dev)) \
-            .clamp_(max=self.max_seq - 1).reshape(-1)          # [n*T]
-        # rows (i, t) that are real, and where their K/V go
-        real = [(i, t) for i in range(n) for t in range(q_lens[i])]
-        real_t = torch.tensor([i * T + t for i, t in real], device=dev)
-        wr_pos = pos[real_t]
-        if self.page_size is None:
-            wr_t = torch.tensor([active[i] for i, _ in real], device=dev)
-        else:
+        if self.page_size is not None:
             for s, ql in zip(active, q_lens):
                 self._grow(s, self.lengths[s] + ql)
-            wr_t = torch.tensor(
-                [self.pages[active[i]][(self.lengths[active[i]] + t)
-                                       // self.page_size] for i, t in real],
-                device=dev)
-            wr_pos = wr_pos % self.page_size
-        wr32, wr_pos32 = wr_t.int(), wr_pos.int()
+        if not all(self._fused):         # the fused prologue needs none
+            pos = (base[:, None] + torch.arange(T, device=dev)) \
+                .clamp_(max=self.max_seq - 1).reshape(-1)          # [n*T]
+            # rows (i, t) that are real, and where their K/V go
+            real = [(i, t) for i in range(n) for t in range(q_lens[i])]
+            real_t = torch.tensor([i * T + t for i, t in real], device=dev)
+            wr_pos = pos[real_t]
+            if self.page_size is None:
+                wr_t = torch.tensor([active[i] for i, _ in real], device=dev)
+            else:
+                wr_t = torch.tensor(
+                    [self.pages[active[i]][(self.lengths[active[i]] + t)
+                                           // self.page_size]
+                     for i, t in real], device=dev)
+                wr_pos = wr_pos % self.page_size
+            wr32, wr_pos32 = wr_t.int(), wr_pos.int()
         paged = {} if self.page_size is None \
             else {"page_table": self.page_table}
         q_lens_t = torch.tensor(q_lens, dtype=torch.int32, device=dev)
@@ -476,25 +526,29 @@ class ContinuousBatchingEngine:
             attn = layer.attention
             residual = h
             x = layer.input_norm(h)
-            q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
-            if getattr(attn, "q_layernorm", None) is not None:
-                q = attn.q_layernorm(q)
-                k = attn.k_layernorm(k)
-            if layer.rotary is not None:
-                cos_t, sin_t = layer.rotary.full_tables(self.max_seq, dev)
-                il = getattr(attn, "rope_interleaved", False)
-                q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
-                k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
-            if cache.fp8:
-                kv_cache_append(k[0][real_t], v[0][real_t], cache.k[li],
-                                cache.v[li], wr32, wr_pos32,
-                                cache.k_scale[li], cache.v_scale[li])
+            if self._fused[li]:
+                q = self._prologue(li, layer, x, lengths_t, q_lens_t, slot32,
+                                   paged)
             else:
-                cache.k[li][wr_t, wr_pos] = k[0][real_t]
-                cache.v[li][wr_t, wr_pos] = v[0][real_t]
+                q, k, v = gen._split_qkv(attn, attn.linear_qkv(x))
+                if getattr(attn, "q_layernorm", None) is not None:
+                    q = attn.q_layernorm(q)
+                    k = attn.k_layernorm(k)
+                if layer.rotary is not None:
+                    cos_t, sin_t = layer.rotary.full_tables(self.max_seq, dev)
+                    il = getattr(attn, "rope_interleaved", False)
+                    q = _rope_rows(q, cos_t[pos], sin_t[pos], il)
+                    k = _rope_rows(k, cos_t[pos], sin_t[pos], il)
+                if cache.fp8:
+                    kv_cache_append(k[0][real_t], v[0][real_t], cache.k[li],
+                                    cache.v[li], wr32, wr_pos32,
+                                    cache.k_scale[li], cache.v_scale[li])
+                else:
+                    cache.k[li][wr_t, wr_pos] = k[0][real_t]
+                    cache.v[li][wr_t, wr_pos] = v[0][real_t]
+                q = q[0].reshape(n, T, *q.shape[2:])
             o = decode_attention_multi(
-                q[0].reshape(n, T, *q.shape[2:]), cache.k[li], cache.v[li],
-                lengths_t, q_lens_t, slot32,
+                q, cache.k[li], cache.v[li], lengths_t, q_lens_t, slot32,
                 window=getattr(gen, "window", None), max_len=max_len,
                 softmax_scale=gen.scale, k_scale=cache.k_scale[li],
                 v_scale=cache.v_scale[li], **paged)

@@ -130,7 +130,8 @@ def apply_rope_qk(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor,
     """q,k: [s, b, h, d] SBH-heads layout. cos=None => no RoPE (learned
     positions, gpt family).  interleaved: GPT-J pairwise rotation
     (eager — the HIP kernel implements the NEOX-half layout; interleaved
-    models are rare enough that the fused path stays NEOX-only)."""
+    models are rare enough that the fused path stays NEOX-only; the serving
+    prologue `ops.rope_kv_append` has both pairings in HIP)."""
     if cos is None:
         return q, k
     if cos.dim() == 3:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Standalone per-kernel microbenchmarks (GPU box).
 
-python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|decode-multi|decode-prefill|norms|elementwise|adam|all] [--iters N]
+python tools/bench_kernels.py [flash|varlen|qkv|qkv-varlen|decode-batched|decode-paged|decode-multi|decode-prefill|decode-prologue|norms|elementwise|adam|all] [--iters N]
 
 Prints per-kernel wall time + achieved TF/s (compute) or GB/s (memory).
 Used with rocprofv3 PMC runs to drive the guide's diagnostic loop.
@@ -520,6 +520,76 @@ def bench_decode_prefill(iters, repeats=9, baseline_only=False):
                               f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
 
 
+def bench_decode_prologue(iters, repeats=9, composition_only=False):
+    """One ops.rope_kv_append call beside the composition it replaces in the
+    serving engine: the split of the packed qkv, the cos/sin gathers,
+    `_rope_rows` on q and k and the cache write (two index_put calls for a
+    bf16 contiguous cache, the row gather and `kv_cache_append` for an e4m3
+    cache with pages of 32; the write indices are built outside the timing).
+    h32/8 d128, n rows of T tokens at mixed lengths.  composition_only skips
+    the op (a build without it)."""
+    from types import SimpleNamespace
+    from hetu_galvatron_amd import ops
+    from hetu_galvatron_amd.runtime.inference import GalvatronGenerator
+    from hetu_galvatron_amd.runtime.serving import _rope_rows
+    G, qpg, d, max_s, page = 8, 4, 128, 4096, 32
+    attn = SimpleNamespace(num_groups_local=G, q_per_group=qpg, head_dim=d)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    ang = torch.arange(max_s, device="cuda")[:, None] * 10000.0 ** (
+        -torch.arange(0, d, 2, device="cuda") / d)[None]
+    cos_t, sin_t = ang.cos(), ang.sin()
+    for n in (1, 8, 32):
+        for T in (1, 4):
+            qkv = torch.randn(1, n * T, G * (qpg + 2) * d, device="cuda",
+                              generator=g).bfloat16()
+            base = torch.randint(1, max_s - T, (n,), device="cuda",
+                                 generator=g)
+            pos = (base[:, None] + torch.arange(T, device="cuda")).reshape(-1)
+            slots = torch.arange(n, device="cuda")
+            slot32 = slots.int()
+            q_lens = torch.full((n,), T, dtype=torch.int32, device="cuda")
+            lengths = base.int() + q_lens
+            real_t = torch.arange(n * T, device="cuda")
+            table = torch.randperm(n * max_s // page, device="cuda",
+                                   generator=g).int().reshape(n, -1)
+            for name, fp8 in (("bf16 contiguous", False),
+                              ("e4m3 page32", True)):
+                if fp8:
+                    shape, dtype = (n * max_s // page, page, G, d), \
+                        torch.float8_e4m3fn
+                    wr_t = table[slots.repeat_interleave(T), pos // page]
+                    wr_pos = (pos % page).int()
+                    kw = {"page_table": table}
+                else:
+                    shape, dtype = (n, max_s, G, d), torch.bfloat16
+                    wr_t, wr_pos, kw = slots.repeat_interleave(T), pos, {}
+                kc = torch.zeros(shape, device="cuda").to(dtype)
+                vc = torch.zeros(shape, device="cuda").to(dtype)
+
+                def composition():
+                    q, k, v = GalvatronGenerator._split_qkv(attn, qkv)
+                    q = _rope_rows(q, cos_t[pos], sin_t[pos])
+                    k = _rope_rows(k, cos_t[pos], sin_t[pos])
+                    if fp8:
+                        ops.kv_cache_append(k[0][real_t], v[0][real_t], kc,
+                                            vc, wr_t, wr_pos)
+                    else:
+                        kc[wr_t, wr_pos] = k[0][real_t]
+                        vc[wr_t, wr_pos] = v[0][real_t]
+                    return q
+
+                rows = [("composition", composition)]
+                if not composition_only:
+                    rows.append(("rope_kv_append", lambda: ops.rope_kv_append(
+                        qkv, G, qpg, cos_t, sin_t, lengths, q_lens, slot32,
+                        kc, vc, **kw)))
+                for label, fn in rows:
+                    t, lo, hi = median_of_windows(fn, iters, repeats)
+                    print(f"decode-prologue n{n:<2d} T{T} {name:15s} "
+                          f"{label:14s} {t*1e6:8.1f} us "
+                          f"[{lo*1e6:.1f}, {hi*1e6:.1f}]")
+
+
 def bench_norms(iters):
     e = ext()
     n, H = 4096, 4096
@@ -614,7 +684,8 @@ def main():
     ap.add_argument("--baseline-only", action="store_true",
                     help="decode-prefill entry: time only copy + flash")
     ap.add_argument("--composition-only", action="store_true",
-                    help="qkv-varlen entry: time only the composition")
+                    help="qkv-varlen and decode-prologue entries: time only "
+                         "the composition")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     fns = {"flash": bench_flash, "norms": bench_norms,
@@ -634,6 +705,8 @@ def main():
            "decode-prefill": lambda it: bench_decode_prefill(
                it, args.repeats, args.baseline_only),
            "qkv-varlen": lambda it: bench_qkv_varlen(
+               it, args.repeats, args.composition_only),
+           "decode-prologue": lambda it: bench_decode_prologue(
                it, args.repeats, args.composition_only)}
     if args.what == "all":
         for f in fns.values():
